@@ -1,6 +1,7 @@
 """Benchmark: Mrays/s of the render path on Dragon 1920x1080 (BASELINE.json metric, config c3).
 
-python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c4|c5|...] [--variant auto|cl|ps|lane|...]
+python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR] [--config c3|c4|c5|...]
+                [--variant auto|cl|ps|lane|...]
 
 One step = one frame rendered by all ranks. Frames follow a small camera orbit around the app's
 eye (app.cpp:88): frame k's eye moves along a 0.5-unit circle, so no two frames of a run trace
@@ -22,23 +23,37 @@ the GPU and exits with its code. --selftest: no GPU; a synthetic fill (pixel ind
 for the render kernel so the launch, shard plan, gather and frame assembly run on CPU (gloo).
 ATR_DIST_BACKEND=gloo rehearses N ranks on one GPU (host-staged gather).
 
-Extra JSON fields: single_frame (one frame per launch, app camera: kernel time from HIP events
-on the launch stream and its Mrays/s), roofline (that kernel: algorithmic bytes per launch /
+A plain run does what the headline figure needs and no more: scene and plan setup, W warmup
+frames, the K timed frames, the result line (metric, value, unit, higher_is_better, dtype,
+ms_per_step = wall milliseconds per timed frame, and the run's config). --dump-outputs DIR: after
+the timed frames, rank 0 writes what the timed path left for its last frame (orbit position
+W + K - 1) as DIR/framebuffer.npy (H x W x 4 float32: the BGRX bytes) and DIR/ray_casts.npy
+(H x W float32; at N > 1 the per-shard-tile sums, float64), 64 MB at most in all: a larger frame
+is written as a fixed seeded sample of its pixels, their indices in DIR/sample_index.npy. The
+scene, the cameras and the seed are fixed, so two runs with the same arguments write the same
+arrays. --check (the frames against one-launch renders) stays an option of its own; everything
+else is behind --full:
+
+Extra JSON fields with --full: total_ray_casts_per_frame, steady_state (64 further frames),
+single_frame (one frame per launch, app camera: kernel time from HIP events on the launch stream and its Mrays/s), roofline (that kernel: algorithmic bytes per launch /
 its average duration, against 8 TB/s; traffic = HBM bytes per launch from rocprofv3 --pmc
 FETCH_SIZE x2 (gfx950 correction) + WRITE_SIZE, separate passes of a child run), cpu_baseline
 (the C oracle, i.e. the reference algorithm restated, on the host's cores and on one thread),
 prep (OBJ load, host and device octree build, upload; untimed for Mrays/s).
 """
 import argparse
+import atexit
 import csv
 import glob
 import json
 import math
 import os
 import re
+import shutil
 import socket
 import subprocess
 import sys
+import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -113,6 +128,66 @@ def cpu_share():
     return max(1, n)
 
 
+def writable_dir(path, prefix):
+    """`path`, created if need be; where it cannot be created or written (a checkout that another
+    user built, a read-only tree), a fresh temporary directory that is removed at exit."""
+    try:
+        os.makedirs(path, exist_ok=True)
+        if os.access(path, os.W_OK | os.X_OK):
+            return path
+    except OSError:
+        pass
+    tmp = tempfile.mkdtemp(prefix=prefix)
+    atexit.register(shutil.rmtree, tmp, ignore_errors=True)
+    return tmp
+
+
+def scene_path(asset):
+    """The asset's OBJ file. The Dragon surrogate is decoded from its committed fixture into the
+    tree's cache on first use (atray_amd.assets); where this user cannot write the tree and the
+    cache is not there yet, it is decoded into a temporary directory instead, and
+    $ATRAY_DRAGON_OBJ points this process and the runs it starts (PMC passes) at that file."""
+    from atray_amd import assets as A
+    try:
+        return A.asset_path(asset)
+    except OSError:
+        out = os.path.join(writable_dir(A.CACHE_DIR, "atray_assets_"), "DragonSurrogate.obj")
+        with open(out, "wb") as f:
+            f.write(A.decode_surrogate_npz())
+        os.environ["ATRAY_DRAGON_OBJ"] = out
+        return A.asset_path(asset)
+
+
+DUMP_BUDGET = 64 * 1000 * 1000  # bytes of array data --dump-outputs writes at most, all files together
+
+
+def dump_outputs(dirname, per_pixel, shape, whole=None, budget=DUMP_BUDGET):
+    """--dump-outputs: per_pixel = {name: float32/float64 array, first axis the frame's pixels},
+    written as DIR/<name>.npy with the pixel axis reshaped to `shape`; whole = {name: small array}
+    written as it is. When all of it exceeds the budget, the same seeded sample of the pixels
+    (sorted indices, the same for every run of a shape) is written of each per-pixel array, and
+    the indices as DIR/sample_index.npy. Returns {name: shape written}."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    whole = dict(whole or {})
+    n = int(np.prod(shape))
+    left = budget - sum(a.nbytes for a in whole.values())
+    row = sum(a.nbytes // max(1, n) for a in per_pixel.values())
+    if per_pixel and row * n > left:
+        keep = max(1, min(n, left // (row + 8)))
+        idx = np.sort(np.random.default_rng(SEED & 0xFFFFFFFF).choice(n, size=keep, replace=False))
+        per_pixel = {k: a[idx] for k, a in per_pixel.items()}
+        whole["sample_index"] = idx.astype(np.float64)
+    else:
+        per_pixel = {k: a.reshape(tuple(shape) + a.shape[1:]) for k, a in per_pixel.items()}
+    written = {}
+    for name, a in {**per_pixel, **whole}.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+        written[name] = list(a.shape)
+    return written
+
+
 # PMC passes of the child run, one counter group per rocprofv3 run (gfx950 block limits: FETCH_SIZE
 # takes 3 of the 4 TCC counters, WRITE_SIZE 2, so each gets its own pass).
 PMC_PASSES = [["FETCH_SIZE"], ["WRITE_SIZE"],
@@ -141,6 +216,7 @@ def pmc_counters(args, kernel_name, path_tail=None):
     info = {}
     kept = []
     base = os.path.join(ROOT, "gpurun_out", "bench_pmc")
+    base = writable_dir(base, "bench_pmc_")  # a tree this user cannot write: a temporary directory instead
     for i, group in enumerate(PMC_PASSES):
         d = os.path.join(base, f"{args.config}_pass{i}")
         os.makedirs(d, exist_ok=True)
@@ -154,6 +230,7 @@ def pmc_counters(args, kernel_name, path_tail=None):
         env = dict(os.environ)
         for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
             env.pop(k, None)
+        env["ROCPROF_TMPDIR"] = d  # the profiler's scratch files beside its output, not in the working directory
         try:
             subprocess.run(cmd, check=True, timeout=300, env=env, stdout=subprocess.DEVNULL,
                            stderr=subprocess.DEVNULL)
@@ -227,9 +304,9 @@ def cpu_baseline(asset, W, H, spp, bounces, use_tree, seconds):
     thread, a strided row sample. Traced rays count every get_intersection_data call (the
     threaded whole-frame run traces the reference's 1-px tile overlaps twice, as its threads do);
     ray_casts is the reference's non-sky count (renderer.cpp:260)."""
-    from atray_amd.assets import CENTERS, asset_path
+    from atray_amd.assets import CENTERS
     from oracle import oracle as O
-    s = O.Scene(asset_path(asset), center=CENTERS[asset], use_tree=use_tree)
+    s = O.Scene(scene_path(asset), center=CENTERS[asset], use_tree=use_tree)
     cam = O.Camera(W, H, spp=spp, bounces=bounces)
     share = cpu_share()
 
@@ -313,12 +390,21 @@ def main():
                          "hybrid_b, path_batch_log2, cluster_size, path_camera_occ, path_bounce_occ, primary_occ, path_sort_bits); outputs never change")
     ap.add_argument("--side", type=int, default=32,
                     help="shard tile side (pixels); 32 balances the 8-way c3 plan ~4%% better than 64 (DESIGN.md §5)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed frames also measure and report everything beside the headline figure: "
+                         "total_ray_casts_per_frame, steady_state, single_frame, roofline (PMC child runs), prep "
+                         "(device octree build) and cpu_baseline; --no-cpu-baseline, --no-pmc, --no-prep and "
+                         "--no-steady drop single legs of it")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes the last timed frame's outputs to DIR/<name>.npy (float32/float64, 64 MB at "
+                         "most in all; a larger frame as a fixed seeded sample of its pixels)")
     ap.add_argument("--cpu-seconds", type=float, default=16.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pmc", action="store_true")
-    ap.add_argument("--no-prep", action="store_true", help="skip the device octree build timing")
+    ap.add_argument("--no-prep", action="store_true", help="with --full: skip the device octree build timing")
     ap.add_argument("--no-steady", action="store_true",
-                    help="skip the steady-state figure (64 further frames in 16-frame launches, after the timed region)")
+                    help="with --full: skip the steady-state figure (64 further frames in 16-frame launches, after "
+                         "the timed region)")
     ap.add_argument("--no-orbit", action="store_true", help="every frame from the app camera")
     ap.add_argument("--streams", type=int, default=0,
                     help="launches in flight (one HIP stream each); 0 = 2 for the 1-spp configs (c1-c3: one "
@@ -513,7 +599,7 @@ def run(args):
 
     import atray_amd.engine as E
     from atray_amd import shard as S
-    from atray_amd.assets import CENTERS, asset_path
+    from atray_amd.assets import CENTERS
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -537,7 +623,7 @@ def run(args):
         variant = args.variant_code
     # ---- scene prep (untimed for Mrays/s; reported under "prep")
     prep = {}
-    path = asset_path(asset)
+    path = scene_path(asset)
     t = time.perf_counter()
     mesh = E.Mesh.load_obj(path)  # load_model_data, parallel chunks (OBJ_loader.cpp:298-340)
     prep["obj_load_ms"] = round((time.perf_counter() - t) * 1e3, 2)
@@ -550,7 +636,7 @@ def run(args):
     eng = E.Engine(local % ndev)
     if args.tuning:
         eng.set_tuning(**{k: int(v) for k, v in (kv.split("=") for kv in args.tuning.split(","))})
-    if use_tree and not args.no_prep and rank == 0:
+    if use_tree and args.full and not args.no_prep and rank == 0:
         tm = {}
         E.Octree.build_device(mesh, 300, local % ndev, timings=tm)  # f3: same tree on the GPU
         prep["octree_device_ms"] = round(tm["wall_ms"], 2)
@@ -893,11 +979,24 @@ def run(args):
         dist.all_reduce(rays)
     rays_total = int(rays.item())
 
+    # ---- --dump-outputs (rank 0): the last timed frame as the timed path left it, i.e. the last
+    # frame of the last launch, before anything below renders into the slots again
+    dumped = None
+    timed_launches = launch_sizes(args.steps, F_, S_)
+    if args.dump_outputs and rank == 0 and timed_launches:
+        q, f = (len(timed_launches) - 1) % S_, timed_launches[-1] - 1
+        fb, cs = (fbs[q][f * own:(f + 1) * own], casts[q][f * own:(f + 1) * own]) if sim else image_views(q, f)
+        px = {"framebuffer": fb.cpu().numpy().view(np.uint8).reshape(-1, 4).astype(np.float32)}
+        if pw == 1 or sim:  # per pixel; at N > 1 the reduced per-tile sums, written whole
+            px["ray_casts"] = cs.cpu().numpy().view(np.uint32).astype(np.float32)
+        dumped = dump_outputs(args.dump_outputs, px, (own,) if sim else (H, W),
+                              None if pw == 1 or sim else {"ray_casts": cs.cpu().numpy().astype(np.float64)})
+
     # ---- check (rank 0): the last S x F frames in the slots against one-launch full-frame renders
     # (framebuffer per pixel; ray_casts per pixel at N = 1, per shard tile at N > 1)
     check = None
     casts_total = None
-    if rank == 0:
+    if rank == 0 and (args.full or args.check):
         ref = torch.zeros(W * H, dtype=torch.int32, device=dev)
         refc = torch.zeros(W * H, dtype=torch.int32, device=dev)
         if pw > 1 and not sim:
@@ -927,6 +1026,52 @@ def run(args):
                         mism += int((want.cpu() != cs.cpu()).sum().item())
         check = mism if args.check else None
         casts_frames = sum(nf for _, nf in last.values())
+
+    def result_line():
+        """The result line of a plain run (rank 0); --full adds its legs to it."""
+        out = {"metric": METRIC, "value": round(rays_total / elapsed / 1e6, 3), "unit": "Mrays/s", "n_gpus": world,
+               "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+               "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32",
+               "data": "synthetic: the survey's Dragon surrogate (Dragon.obj absent), app materials, "
+                       + ("app camera every frame" if args.no_orbit else
+                          f"camera orbit r={ORBIT_RADIUS} around the app eye, {ORBIT_PERIOD} distinct frames"),
+               "config": {"workload": f"{args.config}: {asset} {W}x{H} spp={spp} bounces={bounces} "
+                                      f"{'octree' if use_tree else 'brute-force'}",
+                          "rays_per_step": round(rays_total / args.steps), "shard_tile": args.side,
+                          "parallelism": f"tiles{world}", "kernel": args.variant,
+                          **({"tuning": eng.tuning()} if args.tuning else {}),
+                          "plan": (f"{args.plan}/{args.tile_order}" if pw > 1 else
+                                   "single" if args.single_tiles == "frame" else f"single/{args.tile_order}"),
+                          "streams": args.streams, "frames_per_launch": F_,
+                          **({"exchange": "masked (mask bit + 3 B per non-background px)" if masked else
+                              "bgr (3 B/px)" if bgr else "bgrx (4 B/px)"} if pw > 1 else {}),
+                          "launches": timed_launches,
+                          **({"rank0_extra": round(args.rank0_extra, 4)} if pw > 1 else {}),
+                          "launch_render_done_ms": launch_done,
+                          **({"launch_encoded_ms": launch_encoded} if launch_encoded else {}),
+                          "stream_priority": bool(args.stream_priority),
+                          "cell_plan": cell_split,
+                          "shard_pixels": [int(x) for x in sizes]},
+               **({"sim": {"world": pw, "rank": pr, "note": "one rank's shard rendered alone, no exchange",
+                           "stream_bytes_per_frame": stream_bpf}} if sim else {})}
+        if casts_total is not None:
+            out["total_ray_casts_per_frame"] = round(casts_total / max(1, casts_frames))
+        if (pw > 1 and args.plan in ("cost", "curve")) or args.cell_split or args.cell_order != "list" or \
+            (pw == 1 and args.single_tiles == "cost"):
+            out["config"]["calibration_frames"] = calib_frames(args)  # orbit positions, all before the timed ones
+        if check is not None:
+            out["check_mismatched_pixels"] = check
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
+        return out
+
+    if not args.full:  # a plain run ends here: nothing beside the headline figure is measured
+        if rank == 0:
+            print(json.dumps(result_line()), flush=True)
+        eng.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # ---- the roofline kernel: the timed launches' schedule, one app-camera frame per launch,
     # serialized (AUTO: HYBRID for primary-only frames, the path engine otherwise; capi.cpp auto_sched)
@@ -986,39 +1131,9 @@ def run(args):
 
     if rank == 0:
         value = rays_total / elapsed / 1e6
-        out = {"metric": METRIC, "value": round(value, 3), "unit": "Mrays/s", "n_gpus": world, "steps": args.steps,
-               "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-               "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32",
-               "data": "synthetic: the survey's Dragon surrogate (Dragon.obj absent), app materials, "
-                       + ("app camera every frame" if args.no_orbit else
-                          f"camera orbit r={ORBIT_RADIUS} around the app eye, {ORBIT_PERIOD} distinct frames"),
-               "config": {"workload": f"{args.config}: {asset} {W}x{H} spp={spp} bounces={bounces} "
-                                      f"{'octree' if use_tree else 'brute-force'}",
-                          "rays_per_step": round(rays_total / args.steps), "shard_tile": args.side,
-                          "parallelism": f"tiles{world}", "kernel": args.variant,
-                          **({"tuning": eng.tuning()} if args.tuning else {}),
-                          "plan": (f"{args.plan}/{args.tile_order}" if pw > 1 else
-                                   "single" if args.single_tiles == "frame" else f"single/{args.tile_order}"),
-                          "streams": args.streams, "frames_per_launch": F_,
-                          **({"exchange": "masked (mask bit + 3 B per non-background px)" if masked else
-                              "bgr (3 B/px)" if bgr else "bgrx (4 B/px)"} if pw > 1 else {}),
-                          "launches": launch_sizes(args.steps, F_, S_),
-                          **({"rank0_extra": round(args.rank0_extra, 4)} if pw > 1 else {}),
-                          "launch_render_done_ms": launch_done,
-                          **({"launch_encoded_ms": launch_encoded} if launch_encoded else {}),
-                          "stream_priority": bool(args.stream_priority),
-                          "cell_plan": cell_split,
-                          "shard_pixels": [int(x) for x in sizes]},
-               **({"sim": {"world": pw, "rank": pr, "note": "one rank's shard rendered alone, no exchange",
-                           "stream_bytes_per_frame": stream_bpf}} if sim else {}),
-               "total_ray_casts_per_frame": round(casts_total / max(1, casts_frames))}
+        out = result_line()
         if steady:
             out["steady_state"] = steady
-        if (pw > 1 and args.plan in ("cost", "curve")) or args.cell_split or args.cell_order != "list" or \
-            (pw == 1 and args.single_tiles == "cost"):
-            out["config"]["calibration_frames"] = calib_frames(args)  # orbit positions, all before the timed ones
-        if check is not None:
-            out["check_mismatched_pixels"] = check
         n1 = live_ctr["n_rays"]
         out["single_frame"] = {"kernel_ms": round(kern_ms, 4), "mrays_s": round(n1 / kern_ms / 1e3, 1),
                                "latency_ms": round(lat_ms, 4),

@@ -106,6 +106,68 @@ def test_path_dispatches_count_the_queue_sort():
     assert bench.path_dispatches(A, tiles, 1920, 1080, 64, 1, 28, sort_bits=5).keys() == d0.keys()
 
 
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    """bench.dump_outputs (--dump-outputs): a frame within the budget is written whole in image
+    shape; a larger one as the same seeded pixel sample of every per-pixel array, with the
+    indices, within the budget; the same call writes the same bytes."""
+    import numpy as np
+    H, W = 6, 10
+    fb = np.arange(H * W * 4, dtype=np.float32).reshape(H * W, 4)
+    casts = np.arange(H * W, dtype=np.float32)
+    got = bench.dump_outputs(str(tmp_path / "a"), {"framebuffer": fb, "ray_casts": casts}, (H, W))
+    assert got == {"framebuffer": [H, W, 4], "ray_casts": [H, W]}
+    assert np.array_equal(np.load(tmp_path / "a" / "framebuffer.npy"), fb.reshape(H, W, 4))
+    assert np.array_equal(np.load(tmp_path / "a" / "ray_casts.npy"), casts.reshape(H, W))
+    tiles = np.arange(5, dtype=np.float64)
+    for d in ("b", "c"):
+        got = bench.dump_outputs(str(tmp_path / d), {"framebuffer": fb, "ray_casts": casts}, (H, W),
+                                 {"tile_sums": tiles}, budget=600)
+    n = got["sample_index"][0]
+    assert got == {"framebuffer": [n, 4], "ray_casts": [n], "tile_sums": [5], "sample_index": [n]}
+    files = sorted(os.listdir(tmp_path / "b"))
+    assert files == ["framebuffer.npy", "ray_casts.npy", "sample_index.npy", "tile_sums.npy"]
+    arrs = {f: np.load(tmp_path / "b" / f) for f in files}
+    assert 0 < sum(a.nbytes for a in arrs.values()) <= 600
+    assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+    idx = arrs["sample_index.npy"].astype(np.int64)
+    assert n >= 15 and np.all(np.diff(idx) > 0) and 0 <= idx[0] and idx[-1] < H * W
+    assert np.array_equal(arrs["framebuffer.npy"], fb[idx]) and np.array_equal(arrs["ray_casts.npy"], casts[idx])
+    assert np.array_equal(arrs["tile_sums.npy"], tiles)
+    for f in files:
+        assert (tmp_path / "b" / f).read_bytes() == (tmp_path / "c" / f).read_bytes()
+
+
+def test_scene_path_in_a_tree_that_cannot_be_written(tmp_path, monkeypatch):
+    """bench.scene_path: where the Dragon surrogate's cache directory cannot be created (here a file
+    stands in its way, which stops every user), the OBJ is decoded into a temporary directory
+    outside the tree, byte for byte the fixture's text, and $ATRAY_DRAGON_OBJ names it for the
+    child runs; bench.writable_dir keeps a directory it can write."""
+    import hashlib
+    import numpy as np
+    from atray_amd import assets as A
+    blocker = tmp_path / "blocker"
+    blocker.write_text("")
+    monkeypatch.setattr(A, "CACHE_DIR", str(blocker / "assets"))
+    monkeypatch.setenv("ATRAY_DRAGON_OBJ", "")
+    with pytest.raises(OSError):
+        A.asset_path("Dragon")
+    p = bench.scene_path("Dragon")
+    assert os.environ["ATRAY_DRAGON_OBJ"] == p and os.path.isfile(p)
+    assert not os.path.abspath(p).startswith(ROOT + os.sep) and not p.startswith(str(tmp_path))
+    with open(p, "rb") as f:
+        assert hashlib.sha256(f.read()).digest() == bytes(np.load(A.SURROGATE_NPZ)["sha256"].tolist())
+    assert bench.scene_path("Dragon") == p and bench.scene_path("Cube") == A.asset_path("Cube")
+    ok = tmp_path / "ok" / "sub"
+    assert bench.writable_dir(str(ok), "x_") == str(ok) and ok.is_dir()
+    assert bench.writable_dir(str(blocker / "d"), "x_") != str(blocker / "d")
+
+
+def test_full_and_dump_outputs_are_options():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs DIR" in r.stdout
+
+
 def test_streams_default_per_config():
     """bench.py --streams 0 (default): one for the path-engine configs; for the 1-spp configs one
     while a single launch holds every timed frame (the driver's 20), else two."""

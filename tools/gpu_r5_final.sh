@@ -22,19 +22,19 @@ for step in ${1:-tests c3 c4 c5 trace_c3 trace_c4}; do
     timeout -k 10 120 python3 -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail -20 $O/smoke.log; exit 1; }
     tail -1 $O/smoke.log;;
   c3)
-    timeout -k 10 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_c3.json 2> $O/bench_c3.err || { tail -20 $O/bench_c3.err; exit 1; }
+    timeout -k 10 400 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_c3.json 2> $O/bench_c3.err || { tail -20 $O/bench_c3.err; exit 1; }
     line $O/bench_c3.json;;
   c4)
-    timeout -k 10 500 python3 bench.py --config c4 --steps 8 --warmup 2 $BENCH_ARGS > $O/bench_c4.json 2> $O/bench_c4.err || { tail -20 $O/bench_c4.err; exit 1; }
+    timeout -k 10 500 python3 bench.py --full --config c4 --steps 8 --warmup 2 $BENCH_ARGS > $O/bench_c4.json 2> $O/bench_c4.err || { tail -20 $O/bench_c4.err; exit 1; }
     line $O/bench_c4.json;;
   c5)
-    timeout -k 10 600 python3 bench.py --config c5 --steps 2 --warmup 1 $BENCH_ARGS > $O/bench_c5.json 2> $O/bench_c5.err || { tail -20 $O/bench_c5.err; exit 1; }
+    timeout -k 10 600 python3 bench.py --full --config c5 --steps 2 --warmup 1 $BENCH_ARGS > $O/bench_c5.json 2> $O/bench_c5.err || { tail -20 $O/bench_c5.err; exit 1; }
     line $O/bench_c5.json;;
   trace_c3)
-    timeout -k 10 200 rocprofv3 --kernel-trace --stats -d $O/trace_c3_driver -o run -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-pmc --no-cpu-baseline > $O/trace_c3_driver.log 2>&1 || { tail -20 $O/trace_c3_driver.log; exit 1; }
+    timeout -k 10 200 rocprofv3 --kernel-trace --stats -d $O/trace_c3_driver -o run -- python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-pmc --no-cpu-baseline > $O/trace_c3_driver.log 2>&1 || { tail -20 $O/trace_c3_driver.log; exit 1; }
     echo trace_c3 done;;
   trace_c4)
-    timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/trace_c4 -o run -- python3 bench.py --config c4 --steps 8 --warmup 2 --no-pmc --no-cpu-baseline --no-steady $BENCH_ARGS > $O/trace_c4.log 2>&1 || { tail -20 $O/trace_c4.log; exit 1; }
+    timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/trace_c4 -o run -- python3 bench.py --full --config c4 --steps 8 --warmup 2 --no-pmc --no-cpu-baseline --no-steady $BENCH_ARGS > $O/trace_c4.log 2>&1 || { tail -20 $O/trace_c4.log; exit 1; }
     echo trace_c4 done;;
   esac
 done

@@ -10,7 +10,7 @@ mkdir -p $O
 HB=$!
 trap "kill $HB" EXIT
 run() {  # name, timeout, args
-  timeout -k 10 $2 python3 bench.py --no-pmc --no-cpu-baseline --no-prep --no-steady "${@:3}" > $O/$1.json 2> $O/$1.err || { tail -5 $O/$1.err; exit 1; }
+  timeout -k 10 $2 python3 bench.py --full --no-pmc --no-cpu-baseline --no-prep --no-steady "${@:3}" > $O/$1.json 2> $O/$1.err || { tail -5 $O/$1.err; exit 1; }
   python3 -c "import json; d=json.loads(open('$O/$1.json').read().strip().splitlines()[-1]); print('$1', d['value'], d['ms_per_step'])"
 }
 for cfg in $2; do
