@@ -699,6 +699,8 @@ hipError_t launch_paths_range(atr_ctx* c, const RenderParams& P, hipStream_t s, 
     Q.hyb_b = P.hyb_b;
     Q.nfcam = P.nfcam;
     for (int32_t f = 0; f < P.nfcam; ++f) Q.fcam[f] = P.fcam[f];
+    Q.first_sample = P.first_sample;
+    Q.sample_sum = P.sample_sum;
     if (sort_bits > 0) {
         PathSort& so = Q.sort;
         so.bits = sort_bits;
@@ -747,12 +749,17 @@ hipError_t launch_paths_range(atr_ctx* c, const RenderParams& P, hipStream_t s, 
 // split streams, forked from and joined back into s, so one half's level tails and queue sorts
 // could overlap the other half's tracing; off by default (one c4 frame measured 61.1 vs 60.3 ms,
 // DESIGN.md §4h). Outputs do not depend on the batching.
+// A sample pass (P.sample_sum) is never split, whatever the tuning says: it runs as one range, whose
+// workspace is obtained before any of its kernels is enqueued, so an out-of-memory return leaves
+// the running sums untouched and launch_kernels' FLAT fallback continues from them exactly. A split
+// launch's first half could have added its samples to the sums before the second half failed.
 constexpr int64_t kSplitMinCells = 1024;
 hipError_t launch_paths(atr_ctx* c, const RenderParams& P, hipStream_t s) {
     if (P.nblocks <= 0) return hipSuccess;
     const int64_t per_cell = 64 * std::max<int64_t>(P.cam.samples_per_pixel, 1);
     const int64_t batch = std::max<int64_t>(1, (int64_t(1) << c->tune.path_batch_log2) / per_cell);
-    if (!c->tune.path_split || P.nblocks > batch || P.nblocks < kSplitMinCells || P.counters || P.block_cost)
+    if (!c->tune.path_split || P.nblocks > batch || P.nblocks < kSplitMinCells || P.counters || P.block_cost ||
+        P.sample_sum)
         return launch_paths_range(c, P, s, 0, P.nblocks);
     hipError_t e;
     if (!c->split_fork) {
@@ -1389,6 +1396,61 @@ int atr_render_start_ex(atr_ctx* c, const atr_camera* cam, const atr_tile* tiles
     apply_tuning(c, P);
     HIPCHK(hipEventRecord(c->ev_start, s));
     if ((rc = launch_planned(c, bs, P, wave, s))) return rc;
+    HIPCHK(note_launch(c, s, c->ev_last != c->ev_stop));  // a ring event covers it
+    c->have_render = true;
+    c->last_stream = s;
+    c->last_ntiles = ntiles;
+    return ATR_OK;
+}
+
+// One sample pass of a frame (atray.h): samples [first_sample, first_sample + spp) of every pixel,
+// continuing the running sums in sample_sum. PATHS (the camera kernel's ACCUM flavour and
+// path_resolve_accum_kernel) or the FLAT cell kernel's ACCUM flavour; never HYBRID's primary
+// kernels, also for a one-sample one-bounce pass. The single-frame plan is not applied: a pass is
+// a fraction of a frame, and its cost would train the plan of the tile list's full frames.
+int atr_render_start_samples(atr_ctx* c, const atr_camera* cam, const atr_tile* tiles, int32_t ntiles,
+                             const atr_frame* fr, uint64_t seed, void* stream, int32_t variant,
+                             uint32_t first_sample, float* sample_sum) {
+    if (!c || !cam || !fr || !fr->framebuffer || ntiles < 0 || (ntiles && !tiles)) return ATR_E_INVALID;
+    if (cam->width <= 0 || cam->height <= 0 || cam->width > (1 << 16) || cam->height > (1 << 16)) return ATR_E_INVALID;
+    if (fr->layout != ATR_LAYOUT_IMAGE && fr->layout != ATR_LAYOUT_PACKED) return ATR_E_INVALID;
+    // the stream hash shifts the sample index by 40 bits, and float(total) is exact up to 2^24
+    if (!sample_sum || cam->samples_per_pixel == 0 ||
+        uint64_t(first_sample) + uint64_t(cam->samples_per_pixel) > (uint64_t(1) << 24))
+        return ATR_E_INVALID;
+    if (variant != ATR_KERNEL_AUTO && variant != ATR_KERNEL_PATHS && variant != ATR_KERNEL_FLAT) return ATR_E_INVALID;
+    if (variant == ATR_KERNEL_PATHS && cam->bounce_limit > kMaxPathBounces) return ATR_E_INVALID;
+    if (!c->d_scene) return ATR_E_NOSCENE;
+    HIPCHK(hipSetDevice(c->device));
+    const int sched = variant == ATR_KERNEL_FLAT || cam->bounce_limit > kMaxPathBounces ? sched_of(ATR_KERNEL_FLAT)
+                                                                                         : kSchedPaths;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc = ATR_OK;
+    BlockSet* bs = get_blocks(c, tiles, ntiles, cam->width, cam->height, rc);
+    if (!bs) return rc;
+    c->prog_active = false;
+    RenderParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.cam = *cam;
+    P.scene = c->d_scene;
+    P.seed = seed;
+    P.blocks = static_cast<const DBlock*>(bs->dev.p);
+    P.nblocks = int32_t(bs->host.size());
+    P.layout = fr->layout;
+    P.framebuffer = fr->framebuffer;
+    P.hit_face = fr->hit_face;
+    P.hit_t = fr->hit_t;
+    P.rgb = fr->rgb;
+    P.ray_casts = fr->ray_casts;
+    P.traced_rays = fr->traced_rays;
+    P.error_flag = c->d_error;
+    P.first_sample = first_sample;
+    P.sample_sum = sample_sum;
+    apply_tuning(c, P);
+    HIPCHK(hipEventRecord(c->ev_start, s));
+    hipEvent_t done = nullptr;
+    HIPCHK(launch_render(c, P, sched, s, &done));
+    HIPCHK(record_stop(c, s, done));
     HIPCHK(note_launch(c, s, c->ev_last != c->ev_stop));  // a ring event covers it
     c->have_render = true;
     c->last_stream = s;

@@ -199,6 +199,12 @@ struct RenderParams {
     int32_t hyb_a, hyb_b;  // HYBRID: a step's leaves are dealt in rounds when max clusters > a x rounds + b
     int32_t nfcam;         // > 0: frame f renders with fcam[f] instead of cam (same size/spp/bounces)
     atr_camera fcam[kMaxFrameCams];
+    // A sample pass (atr_render_start_samples): the launch renders samples first_sample ..
+    // first_sample + cam.samples_per_pixel - 1 and continues the f32 sums kept in sample_sum (3 per
+    // output slot, indexed as rgb). Last in the struct and read by the ACCUM kernels only, so every
+    // other kernel's code is what it was without them.
+    uint32_t first_sample;
+    float* sample_sum;     // non-null -> an accumulating pass
 };
 
 // Sample-parallel path engine (paths.hip): one lane per (pixel, sample) path. A batch
@@ -278,6 +284,8 @@ struct PathParams {
     int32_t nfcam;
     PathSort sort;
     atr_camera fcam[kMaxFrameCams];
+    uint32_t first_sample;  // a sample pass (RenderParams): read by the ACCUM camera kernel and
+    float* sample_sum;      // path_resolve_accum_kernel only
 };
 
 }  // namespace atr

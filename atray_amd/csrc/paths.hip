@@ -15,7 +15,9 @@
 //                       its own register budget;
 //   path_resolve_kernel per pixel, the sample colours summed in sample order with the reference's
 //                       f32 adds (col += cast_ray(...), :353-356), then average, clamp, BGRX byte
-//                       conversion (:358-365) -- every output bit-identical to the cell kernels'.
+//                       conversion (:358-365) -- every output bit-identical to the cell kernels';
+//   path_resolve_accum_kernel  the resolve of a sample pass (atr_render_start_samples, DESIGN.md
+//                       §4k): the sums continue from the frame's stored running sums.
 // A batch is a range of the launch's cell list (PathParams, engine.h); the host runs camera,
 // bounces and resolve per batch on one stream (capi.cpp launch_paths).
 #include <hip/hip_runtime.h>
@@ -157,7 +159,11 @@ __device__ __forceinline__ void path_counters(unsigned long long* C, const Ctr& 
 }
 
 // ------------------------------------------------------------------ camera rays + first shading
-template <bool COUNT, int OCC, bool SORT>
+// ACCUM (a sample pass, atr_render_start_samples): the pass's sample s is the frame's sample
+// P.first_sample + s -- its stream, and the primary hit outputs are the frame's sample 0's. The
+// all-sky shortcut stays keyed on the pass's own sample 0: without AA every sample of the pixel,
+// in this pass or another, casts the same camera ray.
+template <bool COUNT, int OCC, bool SORT, bool ACCUM = false>
 __global__ __launch_bounds__(256, OCC) void path_camera_kernel(PathParams P) {
     const int wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6)), lane = threadIdx.x & 63;
     const uint32_t spp = uint32_t(__builtin_amdgcn_readfirstlane(int(P.cam.samples_per_pixel)));
@@ -181,7 +187,9 @@ __global__ __launch_bounds__(256, OCC) void path_camera_kernel(PathParams P) {
     const int32_t x = blk.x0 + (pl & 7), y = blk.y0 + (pl >> 3);
     const int64_t pix = int64_t(y) * cm.width + x;
     uint64_t st, stream;
-    path_stream(P.seed, pix, s, st, stream);
+    uint32_t fs = s;  // the sample's index in the frame
+    if constexpr (ACCUM) fs += P.first_sample;
+    path_stream(P.seed, pix, fs, st, stream);
     const float film_y = -1.0f + 2.0f * (float(y) / float(cm.height));                                  // :317
     const float film_x = ((-1.0f + 2.0f * (float(x) / float(cm.width))) * cm.h_fov) * cm.aspect_ratio;  // :329
     const V3 eye = from(cm.eye), fc = from(cm.frame_center), cx = from(cm.camera_x), cy = from(cm.camera_y);
@@ -201,7 +209,7 @@ __global__ __launch_bounds__(256, OCC) void path_camera_kernel(PathParams P) {
     bool go = false;
     V3 o = eye, ret = mk(0.f, 0.f, 0.f), w = mk(1.f, 1.f, 1.f);
     if (active) {
-        if (s == 0) {  // sample 0's camera ray: the primary hit outputs
+        if (fs == 0) {  // sample 0's camera ray: the primary hit outputs
             const size_t oi = out_index(P.layout, cm.width, P.frame_stride, blk, mask, pl, fidx);
             if (P.hit_face) P.hit_face[oi] = id.face;
             if (P.hit_t) P.hit_t[oi] = id.t;
@@ -356,6 +364,62 @@ __global__ __launch_bounds__(256) void path_resolve_kernel(PathParams P) {
     if (P.ray_casts) P.ray_casts[o] = casts;
 }
 
+// The resolve of a sample pass (atr_render_start_samples): the same cell and lane mapping and row
+// reads, but the sums continue from the pixel's stored running sum (P.sample_sum, the f32 sum of
+// samples [0, first_sample) in sample order; ray_casts likewise) instead of zero, go back there,
+// and the mean is over first_sample + spp samples. The adds are those of a one-shot render of that
+// many samples, in its order, so every output is bit-identical to it. A slot is read and written
+// by the one lane that owns it: no atomics. The primary hit outputs belong to the frame's sample 0,
+// so only the pass with first_sample == 0 writes the miss record.
+__global__ __launch_bounds__(256) void path_resolve_accum_kernel(PathParams P) {
+    const int wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const int32_t cellrel = int32_t(blockIdx.x) * 4 + wave;
+    if (cellrel >= P.ncells) return;
+    int32_t fidx, bi;
+    cell_of(P.frame_blocks, P.nblocks, P.cell0 + cellrel, fidx, bi);
+    const DBlock blk = P.blocks[bi];
+    const uint64_t mask = uint64_t(blk.mask_lo) | (uint64_t(blk.mask_hi) << 32);
+    if (!((mask >> lane) & 1)) return;
+    const atr_camera& cm = P.nfcam > 0 ? P.fcam[__builtin_amdgcn_readfirstlane(fidx)] : P.cam;
+    const uint32_t spp = cm.samples_per_pixel, first = P.first_sample;
+    const bool traced = cm.bounce_limit > 0;
+    const float4_t* src = P.out + int64_t(cellrel) * 64 * int64_t(spp) + lane;
+    const size_t o = out_index(P.layout, cm.width, P.frame_stride, blk, mask, lane, fidx);
+    V3 col = mk(0.f, 0.f, 0.f);
+    uint32_t casts = 0;
+    if (first > 0) {
+        col = mk(P.sample_sum[3 * o], P.sample_sum[3 * o + 1], P.sample_sum[3 * o + 2]);
+        if (P.ray_casts) casts = P.ray_casts[o];
+    }
+    const float4_t v0 = traced && spp > 0 ? src[0] : float4_t{0.f, 0.f, 0.f, 0.f};
+    const bool all_sky = traced && spp > 0 && !cm.anti_aliasing && __float_as_uint(v0.w) == kAllSky;
+    for (uint32_t s = 0; s < spp; ++s) {  // col += cast_ray(...) in sample order (:353-356)
+        V3 c = mk(0.f, 0.f, 0.f);
+        if (all_sky) {
+            c = mk(v0.x, v0.y, v0.z);
+        } else if (traced) {
+            const float4_t v = s == 0 ? v0 : src[64 * int64_t(s)];
+            c = mk(v.x, v.y, v.z);
+            casts += __float_as_uint(v.w);
+        }
+        col = add(col, c);
+    }
+    P.sample_sum[3 * o] = col.x; P.sample_sum[3 * o + 1] = col.y; P.sample_sum[3 * o + 2] = col.z;
+    col = divs(col, float(first + spp));  // :358 over the samples so far
+    const float cr = pl_max(0.0f, pl_min(col.x, 1.0f));
+    const float cg = pl_max(0.0f, pl_min(col.y, 1.0f));
+    const float cb = pl_max(0.0f, pl_min(col.z, 1.0f));
+    const uint32_t r8 = uint32_t(cr * 255.0f) & 0xFFu, g8 = uint32_t(cg * 255.0f) & 0xFFu,
+                   b8 = uint32_t(cb * 255.0f) & 0xFFu;
+    P.framebuffer[o] = b8 | (g8 << 8) | (r8 << 16);  // Set_Pixel (texture.h:27-38)
+    if (first == 0 && (!traced || spp == 0)) {  // no camera ray ran: the miss record
+        if (P.hit_face) P.hit_face[o] = 0xFFFFFFFFu;
+        if (P.hit_t) P.hit_t[o] = kMaxFloat;
+    }
+    if (P.rgb) { P.rgb[3 * o] = col.x; P.rgb[3 * o + 1] = col.y; P.rgb[3 * o + 2] = col.z; }
+    if (P.ray_casts) P.ray_casts[o] = casts;
+}
+
 // ------------------------------------------------------------------ queue sort (PathSort)
 // Level k's bins: block b sums hist[b x kSortChunk ..) into part[b].
 __global__ __launch_bounds__(256) void path_sort_sums(PathSort so) {
@@ -489,6 +553,9 @@ constexpr int kBounceOcc = ATR_BOUNCE_OCC;
 ATR_PATH_KERNELS(false)
 ATR_PATH_KERNELS(true)
 #undef ATR_PATH_KERNELS
+// the sample passes' camera kernel, at the default occupancy (the bounce kernels serve them as they are)
+template __global__ void path_camera_kernel<false, kCameraOcc, false, true>(PathParams);
+template __global__ void path_camera_kernel<false, kCameraOcc, true, true>(PathParams);
 
 }  // namespace atr
 
@@ -497,7 +564,8 @@ namespace {
 template <bool SORT>
 void launch_camera(const atr::PathParams& P, int occ, dim3 g, hipStream_t s) {
     const dim3 b(256);
-    if (P.counters) hipLaunchKernelGGL((atr::path_camera_kernel<true, 4, SORT>), g, b, 0, s, P);
+    if (P.sample_sum) hipLaunchKernelGGL((atr::path_camera_kernel<false, atr::kCameraOcc, SORT, true>), g, b, 0, s, P);
+    else if (P.counters) hipLaunchKernelGGL((atr::path_camera_kernel<true, 4, SORT>), g, b, 0, s, P);
     else if (occ == 5) hipLaunchKernelGGL((atr::path_camera_kernel<false, 5, SORT>), g, b, 0, s, P);
     else if (occ == 6) hipLaunchKernelGGL((atr::path_camera_kernel<false, 6, SORT>), g, b, 0, s, P);
     else hipLaunchKernelGGL((atr::path_camera_kernel<false, 7, SORT>), g, b, 0, s, P);
@@ -548,6 +616,8 @@ extern "C" hipError_t atr_launch_path_sort(const atr::PathParams& P, int ncu, hi
 
 extern "C" hipError_t atr_launch_path_resolve(const atr::PathParams& P, hipStream_t s) {
     if (P.ncells <= 0) return hipSuccess;
-    hipLaunchKernelGGL(atr::path_resolve_kernel, dim3(unsigned((P.ncells + 3) / 4)), dim3(256), 0, s, P);
+    const dim3 g(unsigned((P.ncells + 3) / 4));
+    if (P.sample_sum) hipLaunchKernelGGL(atr::path_resolve_accum_kernel, g, dim3(256), 0, s, P);
+    else hipLaunchKernelGGL(atr::path_resolve_kernel, g, dim3(256), 0, s, P);
     return hipGetLastError();
 }

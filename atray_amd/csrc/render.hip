@@ -105,8 +105,15 @@ __device__ __forceinline__ V3 cast_ray(const DScene* __restrict__ S, V3 o, V3 d,
 // the hit material's (or the sky's) emission; the three rand_bi draws and the bounce ray it builds
 // feed only a second iteration that never runs (renderer.cpp:222-259), so they are skipped --
 // output bit-identical, and far fewer live registers.
-template <int SCHED, bool COUNT, bool PRIMARY, int OCC = 4>
+//
+// ACCUM (a sample pass, atr_render_start_samples; FLAT only): the pass's sample s is the frame's
+// sample P.first_sample + s; the colour sum and ray_casts continue from the pixel's stored values
+// (P.sample_sum, the f32 sum of samples [0, first_sample) in sample order) and go back there, and the
+// mean is over first_sample + spp samples -- the f32 adds of a one-shot render of that many samples,
+// in its order. The primary hit outputs belong to the frame's sample 0.
+template <int SCHED, bool COUNT, bool PRIMARY, int OCC = 4, bool ACCUM = false>
 __global__ __launch_bounds__(256, OCC) void render_kernel(RenderParams P) {
+    static_assert(!ACCUM || (SCHED == SCHED_FLAT && !PRIMARY && !COUNT), "sample passes run on FLAT");
     // the wave index is uniform: in an SGPR, so are the cell and frame indices derived from it
     const int wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6)), lane = threadIdx.x & 63;
     const int b = remap_xcd(blockIdx.x, gridDim.x, P.xcd_chunk) * 4 + wave;
@@ -141,6 +148,15 @@ __global__ __launch_bounds__(256, OCC) void render_kernel(RenderParams P) {
     float hit_t = kMaxFloat;
     V3 col = mk(0.f, 0.f, 0.f);
     const int64_t pix = int64_t(y) * cm.width + x;
+    if constexpr (ACCUM) {
+        if (active && P.first_sample > 0) {  // the running sums of this lane's own output slot
+            size_t o;
+            if (P.layout == ATR_LAYOUT_PACKED) o = size_t(blk.out_base) + __popcll(mask & ((uint64_t(1) << lane) - 1));
+            else o = size_t(y) * size_t(cm.width) + size_t(x);
+            col = mk(P.sample_sum[3 * o], P.sample_sum[3 * o + 1], P.sample_sum[3 * o + 2]);
+            if (P.ray_casts) casts = P.ray_casts[o];
+        }
+    }
     const float film_y = -1.0f + 2.0f * (float(y) / float(cm.height));                       // :317
     const float film_x = ((-1.0f + 2.0f * (float(x) / float(cm.width))) * cm.h_fov) * cm.aspect_ratio;  // :329
     const V3 eye = from(cm.eye), fc = from(cm.frame_center), cx = from(cm.camera_x), cy = from(cm.camera_y);
@@ -161,14 +177,16 @@ __global__ __launch_bounds__(256, OCC) void render_kernel(RenderParams P) {
     } else {
         for (uint32_t s = 0; s < cm.samples_per_pixel; ++s) {
             uint64_t st, stream;
-            path_stream(P.seed, pix, s, st, stream);  // one PCG stream per (pixel, sample), engine.h
+            uint32_t fs = s;  // the sample's index in the frame
+            if constexpr (ACCUM) fs += P.first_sample;
+            path_stream(P.seed, pix, fs, st, stream);  // one PCG stream per (pixel, sample), engine.h
             if (cm.anti_aliasing) {  // :338-343
                 const float xo = rand_bi(st, stream) * cm.half_pixel_width + film_x;
                 const float yo = rand_bi(st, stream) * cm.half_pixel_height + film_y;
                 dir = unit(sub(add(add(fc, scale(cx, xo)), scale(cy, yo)), eye));
             }
             col = add(col, cast_ray<SCHED, COUNT>(S, eye, dir, cm.bounce_limit, active, st, stream, casts, traced,
-                                                 s == 0, hit_face, hit_t, err, ct, P.hyb_a, P.hyb_b, col));
+                                                 fs == 0, hit_face, hit_t, err, ct, P.hyb_a, P.hyb_b, col));
         }
     }
     // the output address from the cell record read again: the pixel coordinates and mask then hold
@@ -181,7 +199,9 @@ __global__ __launch_bounds__(256, OCC) void render_kernel(RenderParams P) {
     olane &= 63;
     const uint64_t omask = uint64_t(ob.mask_lo) | (uint64_t(ob.mask_hi) << 32);
     if ((omask >> olane) & 1) {
-        col = divs(col, float(cm.samples_per_pixel));  // :358
+        [[maybe_unused]] const V3 sum = col;
+        if constexpr (ACCUM) col = divs(col, float(P.first_sample + cm.samples_per_pixel));  // the samples so far
+        else col = divs(col, float(cm.samples_per_pixel));  // :358
         const float cr = pl_max(0.0f, pl_min(col.x, 1.0f));
         const float cg = pl_max(0.0f, pl_min(col.y, 1.0f));
         const float cb = pl_max(0.0f, pl_min(col.z, 1.0f));
@@ -192,8 +212,11 @@ __global__ __launch_bounds__(256, OCC) void render_kernel(RenderParams P) {
         else o = size_t(ob.y0 + (olane >> 3)) * size_t(cm.width) + size_t(ob.x0 + (olane & 7));
         o += size_t(fidx) * size_t(P.frame_stride);
         P.framebuffer[o] = b8 | (g8 << 8) | (r8 << 16);  // Set_Pixel (texture.h:27-38)
-        if (P.hit_face) P.hit_face[o] = hit_face;
-        if (P.hit_t) P.hit_t[o] = hit_t;
+        if (!ACCUM || P.first_sample == 0) {
+            if (P.hit_face) P.hit_face[o] = hit_face;
+            if (P.hit_t) P.hit_t[o] = hit_t;
+        }
+        if constexpr (ACCUM) { P.sample_sum[3 * o] = sum.x; P.sample_sum[3 * o + 1] = sum.y; P.sample_sum[3 * o + 2] = sum.z; }
         if (P.rgb) { P.rgb[3 * o] = col.x; P.rgb[3 * o + 1] = col.y; P.rgb[3 * o + 2] = col.z; }
         if (P.ray_casts) P.ray_casts[o] = casts;
     }
@@ -271,7 +294,7 @@ __global__ __launch_bounds__(256, OCC) void render_kernel(RenderParams P) {
 
 // The shipping instantiations (12): LANE {count} x {primary} + the 5-wave primary; HYBRID primaries
 // at 6 (one frame) / 7 (frames in flight) waves/SIMD, its bounce-loop build and the COUNT builds;
-// FLAT at 6 / 7 waves/SIMD and its COUNT build.
+// FLAT at 6 / 7 waves/SIMD and its COUNT build. Plus FLAT's ACCUM flavour (sample passes).
 template __global__ void render_kernel<SCHED_LANE, false, false>(RenderParams);
 template __global__ void render_kernel<SCHED_LANE, true, false>(RenderParams);
 template __global__ void render_kernel<SCHED_LANE, true, true>(RenderParams);
@@ -285,6 +308,8 @@ template __global__ void render_kernel<SCHED_HYBRID, true, false>(RenderParams);
 template __global__ void render_kernel<SCHED_FLAT, false, false, 6>(RenderParams);
 template __global__ void render_kernel<SCHED_FLAT, false, false, 7>(RenderParams);
 template __global__ void render_kernel<SCHED_FLAT, true, false>(RenderParams);
+// and the sample passes' FLAT kernel (atr_render_start_samples)
+template __global__ void render_kernel<SCHED_FLAT, false, false, 6, true>(RenderParams);
 
 // Sum the 64 traced-ray counters of a launch into the caller's accumulator and clear them.
 __global__ __launch_bounds__(64) void traced_finish_kernel(unsigned long long* __restrict__ slots,
@@ -358,10 +383,10 @@ __global__ __launch_bounds__(256) void packed_tile_casts_kernel(const int32_t* _
 }  // namespace atr
 
 // ------------------------------------------------------------------ launchers used by capi.cpp
-template <int SC, bool C, bool PR, int OCC = 4>
+template <int SC, bool C, bool PR, int OCC = 4, bool ACCUM = false>
 static void launch_one(const atr::RenderParams& P, hipStream_t s) {
     const int grid = (P.nblocks + 3) / 4;
-    hipLaunchKernelGGL((atr::render_kernel<SC, C, PR, OCC>), dim3(grid), dim3(256), 0, s, P);
+    hipLaunchKernelGGL((atr::render_kernel<SC, C, PR, OCC, ACCUM>), dim3(grid), dim3(256), 0, s, P);
 }
 
 // sched: 0 LANE, 6 FLAT, 7 HYBRID (capi.cpp sched_of). Occupancy per schedule and launch shape by
@@ -374,6 +399,11 @@ extern "C" hipError_t atr_launch_render(const atr::RenderParams& P, int sched, i
     const bool count = P.counters != nullptr;
     const bool prim = P.cam.bounce_limit == 1 && !P.cam.anti_aliasing && P.cam.samples_per_pixel == 1;
     const bool multi = P.frame_blocks > 0;
+    if (P.sample_sum) {  // a sample pass: one frame on the FLAT cell kernel's ACCUM flavour
+        if (sched != SCHED_FLAT || count || multi) return hipErrorInvalidValue;
+        launch_one<SCHED_FLAT, false, false, 6, true>(P, s);
+        return hipGetLastError();
+    }
     // default: frames in flight at 7 waves/SIMD, one frame at 8 (one frame alone 0.333 vs 0.345 ms
     // at 6 waves; frames in flight equal at 7 and 8)
     const int occ = primary_occ ? primary_occ : (multi ? 7 : 8);

@@ -114,7 +114,7 @@ EXPORTS = [
     "atr_default_tuning", "atr_set_tuning", "atr_get_tuning", "atr_pack_bgr", "atr_scatter_bgr",
     "atr_pack_bgr_masked_bound", "atr_pack_bgr_masked", "atr_scatter_bgr_masked", "atr_unpack_masked",
     "atr_unpack_masked_ranks",
-    "atr_render_plan_info", "atr_workspace_info",
+    "atr_render_plan_info", "atr_workspace_info", "atr_render_start_samples",
 ]
 # the diagnostic build's extra symbols (include/atray_diag.h; make -C atray_amd/csrc DIAG=1)
 DIAG_EXPORTS = ["atr_render_wave_trace", "atr_render_phase_clocks", "atr_render_path_counters",
@@ -163,6 +163,8 @@ def lib():
         "atr_workspace_info": ([vp, P(i32), P(i64)], C.c_int),
         "atr_render_start": ([vp, P(atr_camera), vp, i32, P(atr_frame), C.c_uint64, vp], C.c_int),
         "atr_render_start_ex": ([vp, P(atr_camera), vp, i32, P(atr_frame), C.c_uint64, vp, i32], C.c_int),
+        "atr_render_start_samples": ([vp, P(atr_camera), vp, i32, P(atr_frame), C.c_uint64, vp, i32, u32, vp],
+                                     C.c_int),
         "atr_render_packed_size": ([vp, i32], i64),
         "atr_render_counters": ([vp, P(atr_camera), vp, i32, C.c_uint64, i32, i64 * 10], C.c_int),
         "atr_render_tile_costs": ([vp, P(atr_camera), vp, i32, C.c_uint64, vp], C.c_int),
@@ -461,6 +463,18 @@ class Engine:
                                         C.byref(frame), C.c_uint64(seed & (2**64 - 1)),
                                         C.c_void_p(stream) if stream else None, int(variant)),
               "render start")
+
+    def render_start_samples(self, cam, tiles, frame: atr_frame, seed, first_sample, sum_ptr, stream=None,
+                             variant=ATR_KERNEL_AUTO):
+        """One sample pass of a frame: samples first_sample .. first_sample + cam.samples_per_pixel - 1,
+        continuing the running sums at sum_ptr (device, 3 f32 per output slot, indexed as frame.rgb).
+        Passes covering [0, N) in order on one stream leave the N-spp render, bit for bit."""
+        arr, n = tiles if isinstance(tiles, tuple) else tiles_array(tiles)
+        check(lib().atr_render_start_samples(self.h, C.byref(cam), C.cast(arr, C.c_void_p), n,
+                                             C.byref(frame), C.c_uint64(seed & (2**64 - 1)),
+                                             C.c_void_p(stream) if stream else None, int(variant),
+                                             int(first_sample), C.c_void_p(sum_ptr) if sum_ptr else None),
+              "sample pass start")
 
     def render_start_progressive(self, cam, tiles, frame: atr_frame, seed, tiles_per_launch, stream=None,
                                  variant=ATR_KERNEL_AUTO):

@@ -131,16 +131,49 @@ class RenderInfo:
     seed: int = 0x853C49E6748FEA9B
     jobs: List[RenderTile] = field(default_factory=list)
     jobs_done: int = 0
+    samples_done: int = 0           # sample-progressive renders: samples per pixel finished so far
     total_ray_casts: int = 0
     _dev: dict = field(default_factory=dict)
 
 
-def start_render_from_camera(info: RenderInfo, engine: E.Engine, tiles_per_launch: int = 0) -> None:
-    """renderer.cpp:447-455. tiles_per_launch > 0 renders progressively for a live view
+def sample_schedule(spp: int) -> List[int]:
+    """The default refinement schedule of a sample-progressive render: passes of 1, 1, 2, 4, ...
+    samples (the samples done double with every pass), the last pass trimmed so they sum to spp:
+    64 -> [1, 1, 2, 4, 8, 16, 32], 100 -> [1, 1, 2, 4, 8, 16, 32, 36]."""
+    spp = int(spp)
+    if spp < 1:
+        raise ValueError("sample_schedule: spp must be at least 1")
+    passes, done = [], 0
+    while done < spp:
+        n = min(max(done, 1), spp - done)
+        passes.append(n)
+        done += n
+    return passes
+
+
+def start_render_from_camera(info: RenderInfo, engine: E.Engine, tiles_per_launch: int = 0,
+                             sample_passes=None) -> None:
+    """renderer.cpp:447-455. tiles_per_launch > 0 renders progressively by tile for a live view
     (app.cpp:162-186): wait_for_render_from_camera_to_finish then reports finished tiles in
-    jobs_done and refreshes camera_tex with them while the render runs."""
+    jobs_done and refreshes camera_tex with them while the render runs.
+
+    sample_passes renders progressively by sample instead: a list of pass sizes summing to the
+    camera's samples_per_pixel, or True for sample_schedule(spp). Every pass renders the whole
+    image (atr_render_start_samples), so a noisy full frame exists after the first pass and
+    wait_for_render_from_camera_to_finish reports the samples finished in samples_done. The final
+    outputs are those of the one-shot render, bit for bit. The two progressive modes do not
+    combine (ValueError)."""
     import torch
     W, H = info.camera.render_settings.resolution
+    spp = int(info.camera.render_settings.samples_per_pixel)
+    if sample_passes is not None and sample_passes is not False:
+        if tiles_per_launch > 0:
+            raise ValueError("start_render_from_camera: tiles_per_launch and sample_passes do not combine")
+        passes = sample_schedule(spp) if sample_passes is True else [int(n) for n in sample_passes]
+        if not passes or min(passes) < 1 or sum(passes) != spp:
+            raise ValueError(f"start_render_from_camera: sample_passes must be positive and sum to {spp}")
+    else:
+        passes = None
     tiles = E.make_tiles(W, H, info.threads)
     info.jobs = [RenderTile(tuple(int(v) for v in t)) for t in tiles]
     info.jobs_done = 0
@@ -150,7 +183,28 @@ def start_render_from_camera(info: RenderInfo, engine: E.Engine, tiles_per_launc
     per_tile = torch.zeros(len(tiles), dtype=torch.int64, device=dev)
     frame = E.atr_frame(E.ATR_LAYOUT_IMAGE, fb.data_ptr(), None, None, None, casts.data_ptr(), None)
     d = {"fb": fb, "casts": casts, "per_tile": per_tile, "tiles": tiles}
-    if tiles_per_launch > 0:
+    info.samples_done = 0
+    if passes is not None:
+        # own stream, as below; one event per pass tells the live view how far the frame is
+        rs = torch.cuda.Stream(dev)
+        rs.wait_stream(torch.cuda.current_stream(dev))
+        d["render_stream"], d["copy_stream"] = rs, torch.cuda.Stream(dev)
+        d["host"] = torch.empty(H * W, dtype=torch.int32, pin_memory=True)
+        d["stream"] = rs.cuda_stream
+        d["sum"] = torch.empty(3 * H * W, dtype=torch.float32, device=dev)  # written by the first pass
+        d["pass_events"], d["pass_totals"] = [], []
+        cam = E.atr_camera.from_buffer_copy(info.camera.c)
+        first = 0
+        for n in passes:
+            cam.samples_per_pixel = n
+            engine.render_start_samples(cam, tiles, frame, info.seed, first, d["sum"].data_ptr(),
+                                        stream=rs.cuda_stream)
+            ev = torch.cuda.Event()
+            ev.record(rs)
+            first += n
+            d["pass_events"].append(ev)
+            d["pass_totals"].append(first)
+    elif tiles_per_launch > 0:
         # own stream, so the live copies (another stream) run beside the render
         rs = torch.cuda.Stream(dev)
         rs.wait_stream(torch.cuda.current_stream(dev))
@@ -179,6 +233,19 @@ def wait_for_render_from_camera_to_finish(info: RenderInfo, engine: E.Engine, ms
     rc, done = engine.wait(ms_to_wait_for)
     d = info._dev
     if rc == 1:
+        if "pass_events" in d:
+            # the passes whose events have completed. The copy below runs beside the next pass, so
+            # it may mix the states after two adjacent passes; each pixel is still a valid mean of
+            # its own sample count (every pass rewrites a pixel with one 4-byte store).
+            total = 0
+            for ev, t in zip(d["pass_events"], d["pass_totals"]):
+                if not ev.query():
+                    break
+                total = t
+            if total > info.samples_done:
+                info.samples_done = total
+                _live_copy(info)
+            return True
         if "copy_stream" in d and done > info.jobs_done:
             info.jobs_done = done
             _live_copy(info)  # the pixels of the first `done` tiles are final
@@ -193,6 +260,8 @@ def wait_for_render_from_camera_to_finish(info: RenderInfo, engine: E.Engine, ms
         j.ray_casts = int(c)
     info.total_ray_casts += int(per_tile.sum())
     info.jobs_done = len(info.jobs)
+    if "pass_totals" in d:
+        info.samples_done = d["pass_totals"][-1]
     info.camera_tex = d["fb"].cpu().numpy().view(np.uint32).reshape(H, W)
     return False
 

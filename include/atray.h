@@ -262,6 +262,35 @@ int atr_render_start_progressive(atr_ctx* ctx, const atr_camera* cam, const atr_
 /* Like atr_render_start with an explicit kernel variant. */
 int atr_render_start_ex(atr_ctx* ctx, const atr_camera* cam, const atr_tile* tiles, int32_t ntiles,
                         const atr_frame* frame, uint64_t seed, void* stream, int32_t variant);
+/* Sample-progressive rendering: one PASS of a single frame. Renders samples first_sample ..
+   first_sample + cam->samples_per_pixel - 1 of every pixel of `tiles` (cam->samples_per_pixel is
+   the pass's size, not the frame's). sample_sum: a DEVICE buffer of 3 floats per output slot, laid
+   out and indexed as frame->rgb (IMAGE or PACKED; not the same memory as rgb), holding the f32 sum
+   of the pixel's sample colours in sample order. first_sample == 0: sample_sum is written, never
+   read. first_sample > 0: it is read as the accumulator's starting value and the new sum is written
+   back. After the pass, with total = first_sample + samples_per_pixel:
+     framebuffer, rgb  sum / float(total), then the usual clamp and quantisation;
+     ray_casts         cumulative (first_sample > 0: read, added to, written back);
+     hit_face, hit_t   written only by the pass with first_sample == 0 (the frame's sample 0, or
+                       the miss record); later passes leave them untouched;
+     traced_rays       accumulates as always.
+   Contract: passes with the same camera (but for samples_per_pixel), tiles, seed, layout and
+   buffers, issued in order on ONE stream and covering [0, N) without gap or overlap, leave every
+   output equal to atr_render_start_ex with samples_per_pixel = N, bit for bit; after each pass
+   every output equals that render with samples_per_pixel = total. (Every (pixel, sample) has its
+   own PCG stream, independent of samples_per_pixel, and a pass performs exactly the one-shot
+   render's f32 additions, continued from the stored sum.) first_sample == 0 with the full sample
+   count equals atr_render_start_ex.
+   Ordering between passes is stream order: they may be enqueued back to back without waiting, and
+   atr_render_wait covers the last one enqueued. Passes of one frame on different streams are the
+   caller's synchronisation problem. The path-engine workspace is sized by the pass, so a frame of
+   many samples can be split into passes that fit a small workspace.
+   ATR_E_INVALID: sample_sum == NULL; samples_per_pixel == 0; first_sample + samples_per_pixel >
+   2^24 (the stream hash and float(total)); a variant other than AUTO, PATHS or FLAT (AUTO: PATHS up
+   to 64 bounces, else FLAT; LANE and HYBRID do not take passes); and atr_render_start_ex's checks. */
+int atr_render_start_samples(atr_ctx* ctx, const atr_camera* cam, const atr_tile* tiles, int32_t ntiles,
+                             const atr_frame* frame, uint64_t seed, void* stream, int32_t variant,
+                             uint32_t first_sample, float* sample_sum);
 /* Frames in flight in one launch (throughput, e.g. a live view rendering ahead): nframes renders
    of the same camera and tiles; frame f's outputs start frame_stride elements after frame f-1's
    (rgb: 3 x frame_stride floats; frame_stride >= the layout's pixels per frame). The cell
