@@ -34,6 +34,9 @@ extern "C" hipError_t atr_launch_path_camera(const atr::PathParams& P, int occ, 
 extern "C" hipError_t atr_launch_path_bounce(const atr::PathParams& P, int ncu, int occ, hipStream_t s);
 extern "C" hipError_t atr_launch_path_resolve(const atr::PathParams& P, hipStream_t s);
 extern "C" hipError_t atr_launch_path_sort(const atr::PathParams& P, int ncu, hipStream_t s);
+extern "C" hipError_t atr_launch_path_live(const atr::PathParams& P, hipStream_t s);
+extern "C" hipError_t atr_launch_path_camera_adaptive(const atr::PathParams& P, int ncu, hipStream_t s);
+extern "C" hipError_t atr_launch_path_resolve_adaptive(const atr::PathParams& P, hipStream_t s);
 extern "C" hipError_t atr_launch_tile_casts(const atr_tile* tiles, int32_t ntiles, int32_t width,
                                             const uint32_t* casts, int64_t* out, hipStream_t s);
 extern "C" hipError_t atr_launch_packed_tile_casts(const int32_t* slot_tile, int64_t nslots, const uint32_t* casts,
@@ -261,6 +264,7 @@ struct atr_ctx {
         int64_t cap = 0;
         int32_t levels = 0;
         int64_t sort_bins = 0;    // queue-sort buffers for this many bins (PathSort), or none
+        bool live = false;        // has the live-list area of adaptive passes (PathLive)
         hipEvent_t ev = nullptr;  // recorded after the latest launch that used `mem`
         uint64_t last_use = 0;
     };
@@ -287,6 +291,11 @@ struct atr_ctx {
     std::vector<std::pair<hipStream_t, hipEvent_t>> stream_ev;
     int32_t wave_slots = 0;  // CUs x 4 SIMDs x 6 waves (single-frame plan policy), 0 until first use
     hipStream_t plan_side = nullptr;  // the single-frame plan kernels' stream (created on first use)
+    // adaptive passes' counts (atr_render_adaptive_info): a ring of 4 u64 per pass, zeroed on the
+    // pass's stream before its kernels add to it; adapt_last = the last pass enqueued (-1: none)
+    static constexpr int kAdaptSlots = 8;
+    unsigned long long* adapt_info = nullptr;
+    int adapt_next = 0, adapt_last = -1;
 };
 
 namespace {
@@ -460,7 +469,8 @@ int auto_sched(int32_t variant, const atr_camera& cam) {
 // The render's completion event (ev_last) is recorded right after the render; the plan kernels
 // run on the plan stream, so atr_render_wait, atr_last_kernel_ms and the next launch on s do not
 // wait for them.
-hipError_t launch_render(atr_ctx* c, RenderParams& P, int sched, hipStream_t s, hipEvent_t* done = nullptr);
+hipError_t launch_render(atr_ctx* c, RenderParams& P, int sched, hipStream_t s, hipEvent_t* done = nullptr,
+                         const PathLive* live = nullptr);
 
 // One completion record per launch: `done` (the traced-ray set's event launch_render recorded after
 // the render) when there is one, else ev_stop.
@@ -560,8 +570,22 @@ size_t sort_bytes(int64_t cap, int64_t bins) {
     return size_t(cap) * 12 + size_t(bins) * 8 + size_t(bins / kSortChunk) * 4;
 }
 
+// The live list of an adaptive pass (PathLive) after everything else (256-B aligned; only in a
+// workspace that an adaptive pass has used): per cell a mask and a first group, per group its
+// cell, per scan chunk three sums, and the control words. A batch of `cap` paths has at most
+// cap / 64 cells and as many groups.
+size_t live_bytes(int64_t cap) {
+    const size_t cells = size_t(cap) / 64 + 1;
+    return cells * 16 + (cells / kLiveChunk + 1) * 12 + 256;
+}
+size_t live_offset(int64_t cap, int32_t levels, int64_t bins) {
+    const size_t b = bins ? sort_offset(cap, levels) + sort_bytes(cap, bins)
+                          : size_t(cap) * 16 * (2 * kPathPlanes + 1) + size_t(levels) * sizeof(PathCtl);
+    return (b + 255) & ~size_t(255);
+}
+
 hipError_t path_workspace(atr_ctx* c, hipStream_t s, int64_t cap, int64_t grow_to, int32_t levels, int64_t sort_bins,
-                          atr_ctx::PathWS*& out) {
+                          bool live, atr_ctx::PathWS*& out) {
     atr_ctx::PathWS* ws = nullptr;
     hipError_t e;
     for (auto& w : c->path_ws)
@@ -582,7 +606,7 @@ hipError_t path_workspace(atr_ctx* c, hipStream_t s, int64_t cap, int64_t grow_t
     if (ws->stream != s && ws->mem.p && (e = hipStreamWaitEvent(s, ws->ev, 0)) != hipSuccess) return e;
     ws->stream = s;
     ws->last_use = ++c->ws_clock;
-    if (ws->cap < cap || ws->levels < levels || ws->sort_bins < sort_bins) {
+    if (ws->cap < cap || ws->levels < levels || ws->sort_bins < sort_bins || (live && !ws->live)) {
         if ((e = hipEventSynchronize(ws->ev)) != hipSuccess) return e;
         if (ws->mem.p && (e = hipFree(ws->mem.p)) != hipSuccess) return e;
         ws->mem = DevBuf();
@@ -590,14 +614,18 @@ hipError_t path_workspace(atr_ctx* c, hipStream_t s, int64_t cap, int64_t grow_t
         int64_t ncap = std::max(ws->cap, ws->cap > 0 && ws->cap < cap ? std::max(cap, grow_to) : cap);
         const int32_t nlev = std::max(ws->levels, levels);
         const int64_t nbins = std::max(ws->sort_bins, sort_bins);
+        const bool nlive = ws->live || live;
+        ws->live = false;
         ws->cap = 0;
         ws->levels = 0;
         ws->sort_bins = 0;
         // 2 queues x kPathPlanes planes + the per-path results, 16 B per entry; the level counters;
-        // the queue-sort buffers
+        // the queue-sort buffers; once an adaptive pass used the workspace, the live list (0.25 B
+        // per entry)
         auto bytes_for = [&](int64_t n) {
-            return nbins ? sort_offset(n, nlev) + sort_bytes(n, nbins)
-                         : size_t(n) * 16 * (2 * kPathPlanes + 1) + size_t(nlev) * sizeof(PathCtl);
+            return nlive ? live_offset(n, nlev, nbins) + live_bytes(n)
+                   : nbins ? sort_offset(n, nlev) + sort_bytes(n, nbins)
+                           : size_t(n) * 16 * (2 * kPathPlanes + 1) + size_t(nlev) * sizeof(PathCtl);
         };
         size_t bytes = bytes_for(ncap);
         e = hipMalloc(&ws->mem.p, bytes);
@@ -616,6 +644,7 @@ hipError_t path_workspace(atr_ctx* c, hipStream_t s, int64_t cap, int64_t grow_t
                     w.cap = 0;
                     w.levels = 0;
                     w.sort_bins = 0;
+                    w.live = false;
                 }
             e = hipMalloc(&ws->mem.p, bytes);
         }
@@ -628,6 +657,7 @@ hipError_t path_workspace(atr_ctx* c, hipStream_t s, int64_t cap, int64_t grow_t
         ws->cap = ncap;
         ws->levels = nlev;
         ws->sort_bins = nbins;
+        ws->live = nlive;
     }
     out = ws;
     return hipSuccess;
@@ -636,7 +666,10 @@ hipError_t path_workspace(atr_ctx* c, hipStream_t s, int64_t cap, int64_t grow_t
 // The sample-parallel path engine (paths.hip) over a cell launch's blocks: the cell list in
 // batches of 2^tuning.path_batch_log2 paths, per batch the camera launch, one launch per further
 // bounce (persistent waves over the previous level's queue) and the per-pixel resolve, all on s.
-hipError_t launch_paths_range(atr_ctx* c, const RenderParams& P, hipStream_t s, int64_t cbeg, int64_t cend) {
+// With `live` (an adaptive pass: its count buffer, tolerance and info slot) every batch first builds
+// its live list, the camera launch traces the list's path groups and the resolve is the adaptive one.
+hipError_t launch_paths_range(atr_ctx* c, const RenderParams& P, hipStream_t s, int64_t cbeg, int64_t cend,
+                              const PathLive* live = nullptr) {
     const int64_t spp = P.cam.samples_per_pixel;
     const int32_t bl = P.cam.bounce_limit;
     if (cend <= cbeg) return hipSuccess;
@@ -651,9 +684,12 @@ hipError_t launch_paths_range(atr_ctx* c, const RenderParams& P, hipStream_t s, 
     int64_t cells = 0;
     // a batch of 2^path_batch_log2 paths, halved while the device cannot hold its workspace (down to
     // 2^16 paths; the outputs do not depend on the batch size); then the same without the queue sort
+    // An adaptive pass has no cell-kernel fallback, so it tries the tuned batch size itself even
+    // below 2^16 paths (other launches with such a tuning get no workspace here and render FLAT).
+    const int32_t lg_min = live ? std::min(16, c->tune.path_batch_log2) : 16;
     for (;;) {
         const int64_t bins = sort_bits > 0 ? int64_t(kSortDirs) * kSortDirs << (3 * sort_bits) : 0;
-        for (int32_t lg = c->tune.path_batch_log2; lg >= 16 && e == hipErrorOutOfMemory; --lg) {
+        for (int32_t lg = c->tune.path_batch_log2; lg >= lg_min && e == hipErrorOutOfMemory; --lg) {
             const int64_t batch = std::max<int64_t>(1, (int64_t(1) << lg) / per_cell);
             cells = std::min<int64_t>(batch, cend - cbeg);
             // capacity: this launch's paths rounded up to 2^24 (at most a full batch): a one-frame c4
@@ -662,7 +698,8 @@ hipError_t launch_paths_range(atr_ctx* c, const RenderParams& P, hipStream_t s, 
             // timed multi-frame run once measured a 4x slower c4 line, round 6)
             const int64_t need = cells * per_cell, gran = int64_t(1) << 24;
             const int64_t cap = std::max(need, std::min((need + gran - 1) / gran * gran, batch * per_cell));
-            e = path_workspace(c, s, cap, std::max(batch * per_cell, cap), std::max(levels, 8), bins, ws);
+            e = path_workspace(c, s, cap, std::max(batch * per_cell, cap), std::max(levels, 8), bins, live != nullptr,
+                               ws);
             if (e == hipSuccess && ws->cap < cap) e = hipErrorOutOfMemory;
         }
         if (e != hipErrorOutOfMemory || sort_bits == 0) break;
@@ -701,6 +738,16 @@ hipError_t launch_paths_range(atr_ctx* c, const RenderParams& P, hipStream_t s, 
     for (int32_t f = 0; f < P.nfcam; ++f) Q.fcam[f] = P.fcam[f];
     Q.first_sample = P.first_sample;
     Q.sample_sum = P.sample_sum;
+    if (live) {
+        Q.live = *live;
+        char* lb = static_cast<char*>(ws->mem.p) + live_offset(ws->cap, ws->levels, ws->sort_bins);
+        const size_t cells = size_t(ws->cap) / 64 + 1;
+        Q.live.mask = reinterpret_cast<uint2_t*>(lb);
+        Q.live.first = reinterpret_cast<uint32_t*>(lb + cells * 8);
+        Q.live.group = Q.live.first + cells;
+        Q.live.part = Q.live.group + cells;
+        Q.live.ctl = reinterpret_cast<PathLiveCtl*>(lb + live_bytes(ws->cap) - 256);
+    }
     if (sort_bits > 0) {
         PathSort& so = Q.sort;
         so.bits = sort_bits;
@@ -724,12 +771,15 @@ hipError_t launch_paths_range(atr_ctx* c, const RenderParams& P, hipStream_t s, 
     for (int64_t c0 = cbeg; c0 < cend; c0 += cells) {
         Q.cell0 = int32_t(c0);
         Q.ncells = int32_t(std::min<int64_t>(cells, cend - c0));
+        if (live && (e = atr_launch_path_live(Q, s)) != hipSuccess) return e;
         if (bl > 0 && spp > 0) {
             if ((e = hipMemsetAsync(Q.ctl, 0, sizeof(PathCtl) * size_t(levels), s)) != hipSuccess) return e;
             if (sort_bits > 0 &&
                 (e = hipMemsetAsync(Q.sort.hist, 0, sizeof(uint32_t) * size_t(Q.sort.nbins), s)) != hipSuccess)
                 return e;
-            if ((e = atr_launch_path_camera(Q, occ_cam, s)) != hipSuccess) return e;
+            if ((e = live ? atr_launch_path_camera_adaptive(Q, c->ncu, s) : atr_launch_path_camera(Q, occ_cam, s)) !=
+                hipSuccess)
+                return e;
             for (int32_t k = 1; k < bl; ++k) {
                 if (sort_bits > 0) {  // level k - 1's queue in key order (the launches zero the bins)
                     Q.bounce = k - 1;
@@ -739,7 +789,7 @@ hipError_t launch_paths_range(atr_ctx* c, const RenderParams& P, hipStream_t s, 
                 if ((e = atr_launch_path_bounce(Q, c->ncu, occ_bounce, s)) != hipSuccess) return e;
             }
         }
-        if ((e = atr_launch_path_resolve(Q, s)) != hipSuccess) return e;
+        if ((e = live ? atr_launch_path_resolve_adaptive(Q, s) : atr_launch_path_resolve(Q, s)) != hipSuccess) return e;
     }
     return hipEventRecord(ws->ev, s);
 }
@@ -783,7 +833,11 @@ hipError_t launch_paths(atr_ctx* c, const RenderParams& P, hipStream_t s) {
     return r;
 }
 
-hipError_t launch_kernels(atr_ctx* c, RenderParams& P, int sched, hipStream_t s) {
+// An adaptive pass (`live`) is the path engine as one range, like a sample pass, and has no
+// fallback: hipErrorOutOfMemory goes back to the caller, returned by launch_paths_range before it
+// enqueues anything.
+hipError_t launch_kernels(atr_ctx* c, RenderParams& P, int sched, hipStream_t s, const PathLive* live = nullptr) {
+    if (live) return launch_paths_range(c, P, s, 0, P.nblocks, live);
     if (sched == kSchedPaths) {
         hipError_t e = launch_paths(c, P, s);
         if (e != hipErrorOutOfMemory) return e;
@@ -799,16 +853,17 @@ hipError_t launch_kernels(atr_ctx* c, RenderParams& P, int sched, hipStream_t s)
 
 // Launch a render schedule; the traced rays go into a zeroed set of 64 spread counters from the
 // ring, then one add to the caller's accumulator.
-hipError_t launch_render(atr_ctx* c, RenderParams& P, int sched, hipStream_t s, hipEvent_t* done) {
+hipError_t launch_render(atr_ctx* c, RenderParams& P, int sched, hipStream_t s, hipEvent_t* done,
+                         const PathLive* live) {
     if (done) *done = nullptr;
-    if (!P.traced_rays) return launch_kernels(c, P, sched, s);
+    if (!P.traced_rays) return launch_kernels(c, P, sched, s, live);
     const int k = c->tnext;
     c->tnext = (k + 1) % kQueueSlots;
     hipError_t e;
     if (c->tused[k] && (e = hipStreamWaitEvent(s, c->tev[k], 0)) != hipSuccess) return e;
     unsigned long long* caller = P.traced_rays;
     P.traced_rays = reinterpret_cast<unsigned long long*>(static_cast<char*>(c->tring) + size_t(k) * kTraceBytes);
-    e = launch_kernels(c, P, sched, s);
+    e = launch_kernels(c, P, sched, s, live);
     if (e == hipSuccess) e = atr_launch_traced_finish(P.traced_rays, caller, s);
     P.traced_rays = caller;
     if (e != hipSuccess) return e;
@@ -1143,6 +1198,7 @@ int atr_destroy(atr_ctx* c) {
     for (hipEvent_t e : c->tev)
         if (e) (void)hipEventDestroy(e);
     if (c->tring) (void)hipFree(c->tring);
+    if (c->adapt_info) (void)hipFree(c->adapt_info);
     if (c->ev_start) (void)hipEventDestroy(c->ev_start);
     if (c->ev_stop) (void)hipEventDestroy(c->ev_stop);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -1455,6 +1511,81 @@ int atr_render_start_samples(atr_ctx* c, const atr_camera* cam, const atr_tile* 
     c->have_render = true;
     c->last_stream = s;
     c->last_ntiles = ntiles;
+    return ATR_OK;
+}
+
+// One adaptive sample pass (atray.h): atr_render_start_samples' PATHS route with a
+// device-side live list, so only the pixels whose count equals first_sample are traced and
+// resolved. The pass's counts go to a slot of the context's info ring, zeroed on the stream first.
+int atr_render_start_adaptive(atr_ctx* c, const atr_camera* cam, const atr_tile* tiles, int32_t ntiles,
+                              const atr_frame* fr, uint64_t seed, void* stream, int32_t variant,
+                              uint32_t first_sample, float* sample_sum, uint32_t* sample_count, float tolerance) {
+    if (!c || !cam || !fr || !fr->framebuffer || ntiles < 0 || (ntiles && !tiles)) return ATR_E_INVALID;
+    if (cam->width <= 0 || cam->height <= 0 || cam->width > (1 << 16) || cam->height > (1 << 16)) return ATR_E_INVALID;
+    if (fr->layout != ATR_LAYOUT_IMAGE && fr->layout != ATR_LAYOUT_PACKED) return ATR_E_INVALID;
+    if (!sample_sum || !sample_count || cam->samples_per_pixel == 0 ||
+        uint64_t(first_sample) + uint64_t(cam->samples_per_pixel) > (uint64_t(1) << 24))
+        return ATR_E_INVALID;
+    if (!(tolerance >= 0.0f) || !std::isfinite(tolerance)) return ATR_E_INVALID;  // also a NaN
+    if (variant != ATR_KERNEL_AUTO && variant != ATR_KERNEL_PATHS) return ATR_E_INVALID;
+    if (cam->bounce_limit > kMaxPathBounces) return ATR_E_INVALID;
+    if (!c->d_scene) return ATR_E_NOSCENE;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc = ATR_OK;
+    BlockSet* bs = get_blocks(c, tiles, ntiles, cam->width, cam->height, rc);
+    if (!bs) return rc;
+    if (!c->adapt_info) HIPCHK(hipMalloc(&c->adapt_info, atr_ctx::kAdaptSlots * 4 * sizeof(unsigned long long)));
+    c->prog_active = false;
+    RenderParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.cam = *cam;
+    P.scene = c->d_scene;
+    P.seed = seed;
+    P.blocks = static_cast<const DBlock*>(bs->dev.p);
+    P.nblocks = int32_t(bs->host.size());
+    P.layout = fr->layout;
+    P.framebuffer = fr->framebuffer;
+    P.hit_face = fr->hit_face;
+    P.hit_t = fr->hit_t;
+    P.rgb = fr->rgb;
+    P.ray_casts = fr->ray_casts;
+    P.traced_rays = fr->traced_rays;
+    P.error_flag = c->d_error;
+    P.first_sample = first_sample;
+    P.sample_sum = sample_sum;
+    apply_tuning(c, P);
+    PathLive live;
+    std::memset(&live, 0, sizeof(live));
+    live.count = sample_count;
+    live.tolerance = tolerance;
+    const int slot = c->adapt_next;
+    live.info = c->adapt_info + 4 * slot;
+    HIPCHK(hipEventRecord(c->ev_start, s));
+    // the next slot of the ring, never the one atr_render_adaptive_info reads now: a call that
+    // fails below (no workspace) has touched nothing the caller can see
+    HIPCHK(hipMemsetAsync(live.info, 0, 4 * sizeof(unsigned long long), s));
+    hipEvent_t done = nullptr;
+    HIPCHK(launch_render(c, P, kSchedPaths, s, &done, &live));
+    c->adapt_next = (slot + 1) % atr_ctx::kAdaptSlots;
+    c->adapt_last = slot;
+    HIPCHK(record_stop(c, s, done));
+    HIPCHK(note_launch(c, s, c->ev_last != c->ev_stop));  // a ring event covers it
+    c->have_render = true;
+    c->last_stream = s;
+    c->last_ntiles = ntiles;
+    return ATR_OK;
+}
+
+int atr_render_adaptive_info(atr_ctx* c, int64_t info_out[4]) {
+    if (!c || !info_out || c->adapt_last < 0) return ATR_E_INVALID;
+    HIPCHK(hipSetDevice(c->device));
+    unsigned long long v[4];
+    HIPCHK(hipMemcpy(v, c->adapt_info + 4 * c->adapt_last, sizeof(v), hipMemcpyDeviceToHost));
+    info_out[0] = int64_t(v[0]);
+    info_out[1] = int64_t(v[1]);
+    info_out[2] = int64_t(v[2]);
+    info_out[3] = int64_t(v[0]) - int64_t(v[3]);  // live at the start minus the newly converged
     return ATR_OK;
 }
 

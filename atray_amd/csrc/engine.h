@@ -255,6 +255,31 @@ struct PathSort {
     uint32_t* part;    // nbins / kSortChunk block sums
 };
 
+// An adaptive sample pass (atr_render_start_adaptive): only the pixels still live --
+// count[o] == first_sample with ATR_SAMPLES_CONVERGED clear, or every pixel when first_sample == 0 --
+// are traced and resolved. Per batch the live-list kernels (paths.hip path_live_*) leave, for cell
+// c of the batch, its live-pixel mask and the first of its camera path groups (a group = 64
+// consecutive paths of one cell's live pixels, pixel-major: ceil(popcount(mask) x spp / 64) per
+// cell, numbered in cell order), and for every group its cell. kLiveChunk cells form one block of
+// the three-phase scan; part holds 3 u32 per chunk (groups, live pixels, live cells).
+constexpr int32_t kLiveChunk = 64;
+struct PathLiveCtl {
+    uint32_t groups;  // camera path groups of the batch
+    uint32_t claim;   // next group to hand out (persistent camera waves)
+};
+struct PathLive {
+    uint32_t* count;    // the caller's sample_count (null: not an adaptive pass)
+    float tolerance;
+    uint2_t* mask;      // per cell of the batch: its live pixels
+    uint32_t* first;    // per cell: its first group (path_live_build leaves the group count here)
+    uint32_t* group;    // per group: its cell
+    uint32_t* part;     // per chunk: groups (scanned in place), live pixels, live cells
+    PathLiveCtl* ctl;
+    // the pass's counts (atr_render_adaptive_info): pixels live at the start, live blocks, camera
+    // path groups, pixels that converged in this pass
+    unsigned long long* info;
+};
+
 struct PathParams {
     atr_camera cam;
     const DScene* scene;
@@ -286,6 +311,7 @@ struct PathParams {
     atr_camera fcam[kMaxFrameCams];
     uint32_t first_sample;  // a sample pass (RenderParams): read by the ACCUM camera kernel and
     float* sample_sum;      // path_resolve_accum_kernel only
+    PathLive live;          // an adaptive pass: read by the path_live_* and *_adaptive kernels only
 };
 
 }  // namespace atr

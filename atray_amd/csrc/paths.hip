@@ -420,6 +420,282 @@ __global__ __launch_bounds__(256) void path_resolve_accum_kernel(PathParams P) {
     if (P.ray_casts) P.ray_casts[o] = casts;
 }
 
+// ------------------------------------------------------------------ adaptive passes (PathLive)
+// The live list of a batch, three phases like the queue sort's bin scan below. Phase 1: one
+// wavefront per cell (a workgroup's four waves take a chunk's kLiveChunk cells, 16 each): lane pl
+// reads its slot's sample count, the ballot is the cell's live mask, and the cell's group count
+// goes where the scan will leave its first group; the chunk's sums go to part.
+__global__ __launch_bounds__(256) void path_live_build(PathParams P) {
+    __shared__ uint32_t ws[4][3];
+    const int wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const uint32_t spp = P.cam.samples_per_pixel, first = P.first_sample;
+    uint32_t tg = 0, tp = 0, tb = 0;
+    for (int j = 0; j < kLiveChunk / 4; ++j) {
+        const int32_t c = int32_t(blockIdx.x) * kLiveChunk + wave * (kLiveChunk / 4) + j;
+        if (c >= P.ncells) break;  // whole wavefront
+        int32_t fidx, bi;
+        cell_of(P.frame_blocks, P.nblocks, P.cell0 + c, fidx, bi);
+        const DBlock blk = P.blocks[bi];
+        const uint64_t mask = uint64_t(blk.mask_lo) | (uint64_t(blk.mask_hi) << 32);
+        bool live = (mask >> lane) & 1;
+        if (live && first > 0) {  // a first pass reads no count; a converged count never equals first (bit 31)
+            const size_t o = out_index(P.layout, P.cam.width, P.frame_stride, blk, mask, lane, fidx);
+            live = P.live.count[o] == first;
+        }
+        const uint64_t lm = __ballot(live);
+        const uint32_t np = uint32_t(__popcll(lm)), ng = (np * spp + 63u) / 64u;
+        if (lane == 0) {
+            P.live.mask[c] = uint2_t{uint32_t(lm), uint32_t(lm >> 32)};
+            P.live.first[c] = ng;
+        }
+        tg += ng;
+        tp += np;
+        tb += np ? 1u : 0u;
+    }
+    if (lane == 0) { ws[wave][0] = tg; ws[wave][1] = tp; ws[wave][2] = tb; }
+    __syncthreads();
+    if (threadIdx.x < 3)
+        P.live.part[3 * blockIdx.x + threadIdx.x] =
+            ws[0][threadIdx.x] + ws[1][threadIdx.x] + ws[2][threadIdx.x] + ws[3][threadIdx.x];
+}
+
+// Phase 2 (one workgroup): the chunks' group sums scanned in place (exclusive), the batch's group
+// total for the camera launch, and the pass's info counts (one thread adds the batch's: batches run
+// one after another on the stream).
+__global__ __launch_bounds__(1024) void path_live_part_scan(PathParams P) {
+    __shared__ uint32_t ws[16], wp[16], wb[16];
+    const int n = (P.ncells + kLiveChunk - 1) / kLiveChunk, per = (n + 1023) / 1024;
+    const int i0 = int(threadIdx.x) * per, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t t = 0, p = 0, b = 0;
+    for (int i = i0; i < i0 + per && i < n; ++i) {
+        t += P.live.part[3 * i];
+        p += P.live.part[3 * i + 1];
+        b += P.live.part[3 * i + 2];
+    }
+    uint32_t inc = t;
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t y = __shfl_up(inc, off);
+        if (lane >= off) inc += y;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        p += __shfl_xor(p, off);
+        b += __shfl_xor(b, off);
+    }
+    if (lane == 63) ws[wave] = inc;
+    if (lane == 0) { wp[wave] = p; wb[wave] = b; }
+    __syncthreads();
+    uint32_t run = inc - t;
+    for (int w = 0; w < wave; ++w) run += ws[w];
+    for (int i = i0; i < i0 + per && i < n; ++i) {
+        const uint32_t v = P.live.part[3 * i];
+        P.live.part[3 * i] = run;
+        run += v;
+    }
+    if (threadIdx.x == 0) {
+        uint32_t groups = 0, pixels = 0, blocks = 0;
+        for (int w = 0; w < 16; ++w) { groups += ws[w]; pixels += wp[w]; blocks += wb[w]; }
+        P.live.ctl->groups = groups;
+        P.live.ctl->claim = 0;
+        P.live.info[0] += pixels;
+        P.live.info[1] += blocks;
+        P.live.info[2] += groups;
+    }
+}
+
+// Phase 3: chunk b's cells, one per lane: each cell's first group (its chunk's start, then a scan
+// over the wave, in cell order: the block list is in dispatch order and neighbouring cells share
+// tree nodes), and the cell of every one of its groups.
+__global__ __launch_bounds__(64) void path_live_scan(PathParams P) {
+    const int lane = threadIdx.x & 63;
+    const int32_t c = int32_t(blockIdx.x) * kLiveChunk + lane;
+    const uint32_t ng = c < P.ncells ? P.live.first[c] : 0u;
+    uint32_t inc = ng;
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t y = __shfl_up(inc, off);
+        if (lane >= off) inc += y;
+    }
+    if (c >= P.ncells) return;
+    const uint32_t start = P.live.part[3 * blockIdx.x] + inc - ng;
+    P.live.first[c] = start;
+    for (uint32_t j = 0; j < ng; ++j) P.live.group[start + j] = uint32_t(c);
+}
+
+// The camera kernel of an adaptive pass: path_camera_kernel's ACCUM flavour (a sibling, so that
+// kernel's instantiations stay what they were), but a wavefront takes one path group of the live
+// list instead of 64 paths of every cell: path r of a cell is sample first_sample + r % spp of the
+// pixel at the (r / spp)-th set bit of the cell's live mask. Result slots keep their layout, so
+// the bounce kernels, the queue sort and the all-sky shortcut serve the pass as they are. The host
+// does not know the group count: either the worst-case grid (every cell live) whose waves beyond
+// the device-side total leave at once, or (ATR_ADAPT_PERSIST) persistent waves that claim groups
+// the way the bounce kernel claims queue entries (DESIGN.md §4l has the measurement).
+#ifndef ATR_ADAPT_PERSIST
+#define ATR_ADAPT_PERSIST 0
+#endif
+constexpr bool kAdaptPersist = ATR_ADAPT_PERSIST != 0;
+constexpr int kAdaptXcdChunk = 16;  // worst-case grid: the live groups dealt over the XCDs in chunks
+template <bool SORT>
+__global__ __launch_bounds__(256, 6) void path_camera_adaptive_kernel(PathParams P) {
+    const int wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const uint32_t spp = uint32_t(__builtin_amdgcn_readfirstlane(int(P.cam.samples_per_pixel)));
+    const uint32_t total = uint32_t(__builtin_amdgcn_readfirstlane(int(P.live.ctl->groups)));
+    const DScene* S = uniform_global(P.scene);
+    const atr_camera& cm = P.cam;
+    const int32_t bl = cm.bounce_limit;
+    uint32_t traced = 0;
+    int err = 0;
+    for (;;) {
+        uint32_t gi;
+        if constexpr (kAdaptPersist) {
+            uint32_t base = 0;
+            if (lane == 0) base = atomicAdd(&P.live.ctl->claim, 1u);
+            gi = uint32_t(__builtin_amdgcn_readfirstlane(int(__shfl(int(base), 0))));
+            if (gi >= total) break;
+        } else {
+            const int64_t wv =
+                int64_t(remap_xcd(blockIdx.x, gridDim.x, P.xcd_chunk > 0 ? P.xcd_chunk : kAdaptXcdChunk)) * 4 + wave;
+            if (wv >= int64_t(total)) break;  // whole wavefront
+            gi = uint32_t(wv);
+        }
+        const int32_t cellrel = __builtin_amdgcn_readfirstlane(int(P.live.group[gi]));
+        const uint32_t g0 = uint32_t(__builtin_amdgcn_readfirstlane(int(P.live.first[cellrel])));
+        const uint2_t lv = P.live.mask[cellrel];
+        const uint64_t live = uint64_t(uint32_t(__builtin_amdgcn_readfirstlane(int(lv.x)))) |
+                              (uint64_t(uint32_t(__builtin_amdgcn_readfirstlane(int(lv.y)))) << 32);
+        const uint32_t r = (gi - g0) * 64u + uint32_t(lane);  // path within the cell's live pixels
+        const bool valid = r < uint32_t(__popcll(live)) * spp;
+        const uint32_t k = valid ? r / spp : 0u;        // the pixel's rank among the live ones
+        const uint32_t s = valid ? r - k * spp : 0u;    // its sample in the pass
+        int pl = 0;  // the k-th set bit of the live mask
+        {
+            uint32_t rem = k;
+#pragma unroll
+            for (int w = 32; w > 0; w >>= 1) {
+                const uint32_t cnt = uint32_t(__popcll((live >> pl) & ((uint64_t(1) << w) - 1)));
+                if (rem >= cnt) { rem -= cnt; pl += w; }
+            }
+            pl &= 63;
+        }
+        const uint32_t g = uint32_t(cellrel) * 64u * spp + s * 64u + uint32_t(pl);  // result slot
+        int32_t fidx, bi;
+        cell_of(P.frame_blocks, P.nblocks, P.cell0 + cellrel, fidx, bi);
+        const DBlock blk = P.blocks[bi];
+        const uint64_t mask = uint64_t(blk.mask_lo) | (uint64_t(blk.mask_hi) << 32);
+        const bool active = valid && ((live >> pl) & 1) && bl > 0;
+        const int32_t x = blk.x0 + (pl & 7), y = blk.y0 + (pl >> 3);
+        const int64_t pix = int64_t(y) * cm.width + x;
+        uint64_t st, stream;
+        const uint32_t fs = s + P.first_sample;  // the sample's index in the frame
+        path_stream(P.seed, pix, fs, st, stream);
+        const float film_y = -1.0f + 2.0f * (float(y) / float(cm.height));                                  // :317
+        const float film_x = ((-1.0f + 2.0f * (float(x) / float(cm.width))) * cm.h_fov) * cm.aspect_ratio;  // :329
+        const V3 eye = from(cm.eye), fc = from(cm.frame_center), cx = from(cm.camera_x), cy = from(cm.camera_y);
+        V3 d;
+        if (cm.anti_aliasing) {  // :338-347, the sample's two jitter draws
+            const float xo = rand_bi(st, stream) * cm.half_pixel_width + film_x;
+            const float yo = rand_bi(st, stream) * cm.half_pixel_height + film_y;
+            d = unit(sub(add(add(fc, scale(cx, xo)), scale(cy, yo)), eye));
+        } else {
+            d = unit(sub(add(add(fc, scale(cx, film_x)), scale(cy, film_y)), eye));  // :350-351
+        }
+        Ctr ct;
+        Isect id;
+        id.type = T_NONE;
+        intersect_scene<SCHED_HYBRID, FLAV_CAMERA, false>(S, eye, d, active, id, err, ct, P.hyb_a, P.hyb_b);
+        bool go = false;
+        V3 o = eye, ret = mk(0.f, 0.f, 0.f), w = mk(1.f, 1.f, 1.f);
+        if (active) {
+            if (fs == 0) {  // sample 0's camera ray: the primary hit outputs
+                const size_t oi = out_index(P.layout, cm.width, P.frame_stride, blk, mask, pl, fidx);
+                if (P.hit_face) P.hit_face[oi] = id.face;
+                if (P.hit_t) P.hit_t[oi] = id.t;
+            }
+            const DMaterial& mat = S->mats[id.material];
+            if (id.type == T_SKY) {  // :225-229 at i = 0
+                ret = add(ret, had(w, mk(mat.ex, mat.ey, mat.ez)));
+                if (cm.anti_aliasing || !ATR_SKY_ELIDE) path_finish(P.out, g, ret, 0u);
+                else if (s == 0) path_finish(P.out, g, ret, kAllSky);  // the pixel's every sample (kAllSky)
+            } else {
+                bounce_shade(mat, id, o, d, ret, w, st, stream);  // :231-258
+                if (bl <= 1) path_finish(P.out, g, ret, uint32_t(bl));  // ran to the limit (:260)
+                else go = true;
+            }
+            traced += 1;
+        }
+        path_enqueue<SORT>(P.q[0], P.cap, &P.ctl[0], go, o, d, uint32_t(pix), g, ret, w, st, P.sort);
+        if constexpr (!kAdaptPersist) break;
+    }
+    if (P.traced_rays) add_traced(P.traced_rays, traced, int(blockIdx.x * 4 + wave));
+    if (err && P.error_flag) atomicOr(P.error_flag, 1);
+}
+
+// The resolve of an adaptive pass: path_resolve_accum_kernel's arithmetic for the live lanes of a
+// live cell, then the slot's sample count and the stopping rule (atray.h: separately rounded f32
+// operations, -ffp-contract=off). A lane that is not live reads and writes nothing. A slot is owned
+// by one lane; the only atomic is the wave's count of newly converged pixels.
+__global__ __launch_bounds__(256) void path_resolve_adaptive_kernel(PathParams P) {
+    const int wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const int32_t cellrel = int32_t(blockIdx.x) * 4 + wave;
+    if (cellrel >= P.ncells) return;
+    const uint2_t lv = P.live.mask[cellrel];
+    const uint64_t live = uint64_t(lv.x) | (uint64_t(lv.y) << 32);
+    if (live == 0) return;  // whole wavefront
+    int32_t fidx, bi;
+    cell_of(P.frame_blocks, P.nblocks, P.cell0 + cellrel, fidx, bi);
+    const DBlock blk = P.blocks[bi];
+    const uint64_t mask = uint64_t(blk.mask_lo) | (uint64_t(blk.mask_hi) << 32);
+    const atr_camera& cm = P.cam;
+    const uint32_t spp = cm.samples_per_pixel, first = P.first_sample;
+    const bool traced = cm.bounce_limit > 0;
+    bool conv = false;
+    if ((live >> lane) & 1) {
+        const float4_t* src = P.out + int64_t(cellrel) * 64 * int64_t(spp) + lane;
+        const size_t o = out_index(P.layout, cm.width, P.frame_stride, blk, mask, lane, fidx);
+        V3 col = mk(0.f, 0.f, 0.f), before = col;
+        uint32_t casts = 0;
+        if (first > 0) {
+            col = mk(P.sample_sum[3 * o], P.sample_sum[3 * o + 1], P.sample_sum[3 * o + 2]);
+            before = col;
+            if (P.ray_casts) casts = P.ray_casts[o];
+        }
+        const float4_t v0 = traced ? src[0] : float4_t{0.f, 0.f, 0.f, 0.f};
+        const bool all_sky = traced && !cm.anti_aliasing && __float_as_uint(v0.w) == kAllSky;
+        for (uint32_t s = 0; s < spp; ++s) {  // col += cast_ray(...) in sample order (:353-356)
+            V3 c = mk(0.f, 0.f, 0.f);
+            if (all_sky) {
+                c = mk(v0.x, v0.y, v0.z);
+            } else if (traced) {
+                const float4_t v = s == 0 ? v0 : src[64 * int64_t(s)];
+                c = mk(v.x, v.y, v.z);
+                casts += __float_as_uint(v.w);
+            }
+            col = add(col, c);
+        }
+        P.sample_sum[3 * o] = col.x; P.sample_sum[3 * o + 1] = col.y; P.sample_sum[3 * o + 2] = col.z;
+        col = divs(col, float(first + spp));  // :358 over the samples so far
+        const float cr = pl_max(0.0f, pl_min(col.x, 1.0f));
+        const float cg = pl_max(0.0f, pl_min(col.y, 1.0f));
+        const float cb = pl_max(0.0f, pl_min(col.z, 1.0f));
+        const uint32_t r8 = uint32_t(cr * 255.0f) & 0xFFu, g8 = uint32_t(cg * 255.0f) & 0xFFu,
+                       b8 = uint32_t(cb * 255.0f) & 0xFFu;
+        P.framebuffer[o] = b8 | (g8 << 8) | (r8 << 16);  // Set_Pixel (texture.h:27-38)
+        if (first == 0 && !traced) {  // no camera ray ran: the miss record
+            if (P.hit_face) P.hit_face[o] = 0xFFFFFFFFu;
+            if (P.hit_t) P.hit_t[o] = kMaxFloat;
+        }
+        if (P.rgb) { P.rgb[3 * o] = col.x; P.rgb[3 * o + 1] = col.y; P.rgb[3 * o + 2] = col.z; }
+        if (P.ray_casts) P.ray_casts[o] = casts;
+        if (first > 0) {  // the mean moved by less than tolerance x its brightness (false for a NaN)
+            const V3 a = divs(before, float(first));
+            const float dd = (fabsf(col.x - a.x) + fabsf(col.y - a.y)) + fabsf(col.z - a.z);
+            const float l = ((col.x + col.y) + col.z) + 0.01f;
+            conv = dd < P.live.tolerance * l;
+        }
+        P.live.count[o] = (first + spp) | (conv ? ATR_SAMPLES_CONVERGED : 0u);
+    }
+    const uint64_t cvm = __ballot(conv);
+    if (lane == 0 && cvm) atomicAdd(P.live.info + 3, (unsigned long long)__popcll(cvm));
+}
+
 // ------------------------------------------------------------------ queue sort (PathSort)
 // Level k's bins: block b sums hist[b x kSortChunk ..) into part[b].
 __global__ __launch_bounds__(256) void path_sort_sums(PathSort so) {
@@ -556,6 +832,10 @@ ATR_PATH_KERNELS(true)
 // the sample passes' camera kernel, at the default occupancy (the bounce kernels serve them as they are)
 template __global__ void path_camera_kernel<false, kCameraOcc, false, true>(PathParams);
 template __global__ void path_camera_kernel<false, kCameraOcc, true, true>(PathParams);
+// the adaptive passes' camera kernel (its launch bounds name the same occupancy)
+static_assert(kCameraOcc == 6, "path_camera_adaptive_kernel's launch bounds");
+template __global__ void path_camera_adaptive_kernel<false>(PathParams);
+template __global__ void path_camera_adaptive_kernel<true>(PathParams);
 
 }  // namespace atr
 
@@ -611,6 +891,32 @@ extern "C" hipError_t atr_launch_path_sort(const atr::PathParams& P, int ncu, hi
     hipLaunchKernelGGL(atr::path_sort_part_scan, dim3(1), dim3(1024), 0, s, P.sort);
     hipLaunchKernelGGL(atr::path_sort_scan, dim3(blocks), dim3(256), 0, s, P.sort);
     hipLaunchKernelGGL(atr::path_sort_rank, dim3(unsigned(ncu) * 16u), dim3(256), 0, s, P);
+    return hipGetLastError();
+}
+
+// An adaptive pass (P.live): the batch's live list, its camera launch (the worst-case grid, or `ncu`
+// x occupancy persistent workgroups) and its resolve.
+extern "C" hipError_t atr_launch_path_live(const atr::PathParams& P, hipStream_t s) {
+    if (P.ncells <= 0) return hipSuccess;
+    const unsigned chunks = unsigned((P.ncells + atr::kLiveChunk - 1) / atr::kLiveChunk);
+    hipLaunchKernelGGL(atr::path_live_build, dim3(chunks), dim3(256), 0, s, P);
+    hipLaunchKernelGGL(atr::path_live_part_scan, dim3(1), dim3(1024), 0, s, P);
+    hipLaunchKernelGGL(atr::path_live_scan, dim3(chunks), dim3(64), 0, s, P);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t atr_launch_path_camera_adaptive(const atr::PathParams& P, int ncu, hipStream_t s) {
+    const int64_t waves = int64_t(P.ncells) * P.cam.samples_per_pixel;
+    if (waves <= 0) return hipSuccess;
+    const dim3 g(atr::kAdaptPersist ? unsigned(ncu) * unsigned(atr::kCameraOcc) : unsigned((waves + 3) / 4));
+    if (P.sort.bits) hipLaunchKernelGGL(atr::path_camera_adaptive_kernel<true>, g, dim3(256), 0, s, P);
+    else hipLaunchKernelGGL(atr::path_camera_adaptive_kernel<false>, g, dim3(256), 0, s, P);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t atr_launch_path_resolve_adaptive(const atr::PathParams& P, hipStream_t s) {
+    if (P.ncells <= 0) return hipSuccess;
+    hipLaunchKernelGGL(atr::path_resolve_adaptive_kernel, dim3(unsigned((P.ncells + 3) / 4)), dim3(256), 0, s, P);
     return hipGetLastError();
 }
 

@@ -32,6 +32,7 @@ ATR_KERNEL_PATHS = 10
 # the kernel variants of the shipping library (atray.h); AUTO picks HYBRID or PATHS
 VARIANTS = (ATR_KERNEL_LANE, ATR_KERNEL_FLAT, ATR_KERNEL_HYBRID, ATR_KERNEL_PATHS)
 MISS = 0xFFFFFFFF
+ATR_SAMPLES_CONVERGED = 0x80000000  # sample_count bit 31: the pixel has stopped (atr_render_start_adaptive)
 MAX_FLOAT = np.float32(3.402823466e38)
 
 ERRORS = {-1: "ATR_E_INVALID", -2: "ATR_E_IO", -3: "ATR_E_NOMEM", -4: "ATR_E_NOSCENE",
@@ -115,6 +116,7 @@ EXPORTS = [
     "atr_pack_bgr_masked_bound", "atr_pack_bgr_masked", "atr_scatter_bgr_masked", "atr_unpack_masked",
     "atr_unpack_masked_ranks",
     "atr_render_plan_info", "atr_workspace_info", "atr_render_start_samples",
+    "atr_render_start_adaptive", "atr_render_adaptive_info",
 ]
 # the diagnostic build's extra symbols (include/atray_diag.h; make -C atray_amd/csrc DIAG=1)
 DIAG_EXPORTS = ["atr_render_wave_trace", "atr_render_phase_clocks", "atr_render_path_counters",
@@ -165,6 +167,9 @@ def lib():
         "atr_render_start_ex": ([vp, P(atr_camera), vp, i32, P(atr_frame), C.c_uint64, vp, i32], C.c_int),
         "atr_render_start_samples": ([vp, P(atr_camera), vp, i32, P(atr_frame), C.c_uint64, vp, i32, u32, vp],
                                      C.c_int),
+        "atr_render_start_adaptive": ([vp, P(atr_camera), vp, i32, P(atr_frame), C.c_uint64, vp, i32, u32, vp, vp,
+                                       C.c_float], C.c_int),
+        "atr_render_adaptive_info": ([vp, i64 * 4], C.c_int),
         "atr_render_packed_size": ([vp, i32], i64),
         "atr_render_counters": ([vp, P(atr_camera), vp, i32, C.c_uint64, i32, i64 * 10], C.c_int),
         "atr_render_tile_costs": ([vp, P(atr_camera), vp, i32, C.c_uint64, vp], C.c_int),
@@ -475,6 +480,27 @@ class Engine:
                                              C.c_void_p(stream) if stream else None, int(variant),
                                              int(first_sample), C.c_void_p(sum_ptr) if sum_ptr else None),
               "sample pass start")
+
+    def render_start_adaptive(self, cam, tiles, frame: atr_frame, seed, first_sample, sum_ptr, count_ptr, tolerance,
+                              stream=None, variant=ATR_KERNEL_AUTO):
+        """One adaptive sample pass: render_start_samples for the pixels still live only -- those whose
+        u32 at count_ptr (device, one per output slot) equals first_sample with ATR_SAMPLES_CONVERGED
+        clear; every pixel when first_sample is 0. A live pixel whose mean moved by less than
+        tolerance x its brightness gets the flag and stops for good (atray.h has the rule)."""
+        arr, n = tiles if isinstance(tiles, tuple) else tiles_array(tiles)
+        check(lib().atr_render_start_adaptive(self.h, C.byref(cam), C.cast(arr, C.c_void_p), n,
+                                              C.byref(frame), C.c_uint64(seed & (2**64 - 1)),
+                                              C.c_void_p(stream) if stream else None, int(variant),
+                                              int(first_sample), C.c_void_p(sum_ptr) if sum_ptr else None,
+                                              C.c_void_p(count_ptr) if count_ptr else None, float(tolerance)),
+              "adaptive pass start")
+
+    def adaptive_info(self):
+        """The last adaptive pass's counts, once wait() returned 0: (pixels live at its start, blocks
+        with a live pixel, camera path groups traced, pixels still live after it)."""
+        out = (C.c_int64 * 4)()
+        check(lib().atr_render_adaptive_info(self.h, out), "adaptive info")
+        return tuple(int(x) for x in out)
 
     def render_start_progressive(self, cam, tiles, frame: atr_frame, seed, tiles_per_launch, stream=None,
                                  variant=ATR_KERNEL_AUTO):

@@ -133,6 +133,8 @@ class RenderInfo:
     jobs_done: int = 0
     samples_done: int = 0           # sample-progressive renders: samples per pixel finished so far
     total_ray_casts: int = 0
+    sample_counts: np.ndarray = None  # adaptive renders: H x W uint32 samples per pixel, refreshed with camera_tex
+    pixels_live: int = 0              # adaptive renders: pixels the last pass left live (0: every pixel stopped)
     _dev: dict = field(default_factory=dict)
 
 
@@ -152,7 +154,7 @@ def sample_schedule(spp: int) -> List[int]:
 
 
 def start_render_from_camera(info: RenderInfo, engine: E.Engine, tiles_per_launch: int = 0,
-                             sample_passes=None) -> None:
+                             sample_passes=None, adaptive_tolerance=None) -> None:
     """renderer.cpp:447-455. tiles_per_launch > 0 renders progressively by tile for a live view
     (app.cpp:162-186): wait_for_render_from_camera_to_finish then reports finished tiles in
     jobs_done and refreshes camera_tex with them while the render runs.
@@ -162,7 +164,13 @@ def start_render_from_camera(info: RenderInfo, engine: E.Engine, tiles_per_launc
     image (atr_render_start_samples), so a noisy full frame exists after the first pass and
     wait_for_render_from_camera_to_finish reports the samples finished in samples_done. The final
     outputs are those of the one-shot render, bit for bit. The two progressive modes do not
-    combine (ValueError)."""
+    combine (ValueError).
+
+    adaptive_tolerance (with sample_passes) enqueues the schedule through atr_render_start_adaptive:
+    a pixel whose mean moved by less than tolerance x its brightness in a pass takes no further
+    samples. sample_counts then tells how many each pixel got (every pixel's outputs are the one-shot
+    render's at its own count) and pixels_live how many were still refining at the end. Tolerance 0
+    stops nothing and equals the plain schedule. Without sample_passes it is a ValueError."""
     import torch
     W, H = info.camera.render_settings.resolution
     spp = int(info.camera.render_settings.samples_per_pixel)
@@ -174,6 +182,12 @@ def start_render_from_camera(info: RenderInfo, engine: E.Engine, tiles_per_launc
             raise ValueError(f"start_render_from_camera: sample_passes must be positive and sum to {spp}")
     else:
         passes = None
+    if adaptive_tolerance is not None:
+        if passes is None:
+            raise ValueError("start_render_from_camera: adaptive_tolerance needs sample_passes")
+        adaptive_tolerance = float(adaptive_tolerance)
+        if not (0.0 <= adaptive_tolerance < float("inf")):
+            raise ValueError("start_render_from_camera: adaptive_tolerance must be finite and not negative")
     tiles = E.make_tiles(W, H, info.threads)
     info.jobs = [RenderTile(tuple(int(v) for v in t)) for t in tiles]
     info.jobs_done = 0
@@ -184,6 +198,7 @@ def start_render_from_camera(info: RenderInfo, engine: E.Engine, tiles_per_launc
     frame = E.atr_frame(E.ATR_LAYOUT_IMAGE, fb.data_ptr(), None, None, None, casts.data_ptr(), None)
     d = {"fb": fb, "casts": casts, "per_tile": per_tile, "tiles": tiles}
     info.samples_done = 0
+    info.sample_counts, info.pixels_live = None, 0
     if passes is not None:
         # own stream, as below; one event per pass tells the live view how far the frame is
         rs = torch.cuda.Stream(dev)
@@ -193,12 +208,19 @@ def start_render_from_camera(info: RenderInfo, engine: E.Engine, tiles_per_launc
         d["stream"] = rs.cuda_stream
         d["sum"] = torch.empty(3 * H * W, dtype=torch.float32, device=dev)  # written by the first pass
         d["pass_events"], d["pass_totals"] = [], []
+        if adaptive_tolerance is not None:
+            d["count"] = torch.empty(H * W, dtype=torch.int32, device=dev)  # written by the first pass
+            d["host_count"] = torch.empty(H * W, dtype=torch.int32, pin_memory=True)
         cam = E.atr_camera.from_buffer_copy(info.camera.c)
         first = 0
         for n in passes:
             cam.samples_per_pixel = n
-            engine.render_start_samples(cam, tiles, frame, info.seed, first, d["sum"].data_ptr(),
-                                        stream=rs.cuda_stream)
+            if adaptive_tolerance is not None:
+                engine.render_start_adaptive(cam, tiles, frame, info.seed, first, d["sum"].data_ptr(),
+                                             d["count"].data_ptr(), adaptive_tolerance, stream=rs.cuda_stream)
+            else:
+                engine.render_start_samples(cam, tiles, frame, info.seed, first, d["sum"].data_ptr(),
+                                            stream=rs.cuda_stream)
             ev = torch.cuda.Event()
             ev.record(rs)
             first += n
@@ -218,14 +240,22 @@ def start_render_from_camera(info: RenderInfo, engine: E.Engine, tiles_per_launc
     info._dev = d
 
 
+def _strip_flag(counts) -> np.ndarray:
+    return counts.view(np.uint32) & np.uint32(E.ATR_SAMPLES_CONVERGED - 1)
+
+
 def _live_copy(info: RenderInfo) -> None:
     import torch
     d = info._dev
     W, H = info.camera.render_settings.resolution
     with torch.cuda.stream(d["copy_stream"]):
         d["host"].copy_(d["fb"], non_blocking=True)
+        if "count" in d:
+            d["host_count"].copy_(d["count"], non_blocking=True)
     d["copy_stream"].synchronize()
     info.camera_tex = d["host"].numpy().view(np.uint32).reshape(H, W).copy()
+    if "count" in d:
+        info.sample_counts = _strip_flag(d["host_count"].numpy()).reshape(H, W)
 
 
 def wait_for_render_from_camera_to_finish(info: RenderInfo, engine: E.Engine, ms_to_wait_for: int) -> bool:
@@ -263,6 +293,9 @@ def wait_for_render_from_camera_to_finish(info: RenderInfo, engine: E.Engine, ms
     if "pass_totals" in d:
         info.samples_done = d["pass_totals"][-1]
     info.camera_tex = d["fb"].cpu().numpy().view(np.uint32).reshape(H, W)
+    if "count" in d:
+        info.sample_counts = _strip_flag(d["count"].cpu().numpy()).reshape(H, W)
+        info.pixels_live = engine.adaptive_info()[3]
     return False
 
 

@@ -291,6 +291,42 @@ int atr_render_start_ex(atr_ctx* ctx, const atr_camera* cam, const atr_tile* til
 int atr_render_start_samples(atr_ctx* ctx, const atr_camera* cam, const atr_tile* tiles, int32_t ntiles,
                              const atr_frame* frame, uint64_t seed, void* stream, int32_t variant,
                              uint32_t first_sample, float* sample_sum);
+/* Adaptive sampling: a sample pass (atr_render_start_samples) that skips the pixels that have
+   stopped. sample_count: a DEVICE buffer of one u32 per output slot, indexed as frame->rgb and
+   sample_sum: the samples the pixel has received, and bit 31 (ATR_SAMPLES_CONVERGED) once it has
+   stopped for good. A pixel is LIVE in a pass iff first_sample == 0, or sample_count[o] ==
+   first_sample exactly with the flag clear. first_sample == 0: sample_count and sample_sum are
+   written, never read.
+   A live pixel does exactly what it does in atr_render_start_samples, then sample_count[o] =
+   first_sample + n (n = cam->samples_per_pixel), and if first_sample > 0 it is tested, in separately
+   rounded f32 operations (sum_before, sum_after: its sample_sum before and after the pass):
+     a = sum_before / float(first_sample)         m = sum_after / float(first_sample + n)   (= rgb)
+     d = (|m.x - a.x| + |m.y - a.y|) + |m.z - a.z|        l = ((m.x + m.y) + m.z) + 0.01f
+     converged iff d < tolerance * l      (strict: tolerance 0 never stops a pixel; nor does a NaN)
+   and a converged pixel gets ATR_SAMPLES_CONVERGED OR-ed into its count. The first pass tests
+   nothing: its size is the caller's minimum sample count.
+   A pixel that is not live: nothing of it but its count is read, none of its outputs (framebuffer,
+   rgb, ray_casts, sample_sum, sample_count, hit_*) is written and it traces no ray, so traced_rays
+   grows by the live pixels' rays only. Hence after any number of passes every pixel's outputs equal
+   the one-shot render with samples_per_pixel = that pixel's own count, bit for bit.
+   The path engine only (variant AUTO or PATHS, at most 64 bounces); there is no fallback to a cell
+   kernel: if no path workspace can be had the call returns -(1000 + hipErrorOutOfMemory) before
+   anything is enqueued, every buffer untouched. Nothing is read back to the host: passes may be
+   enqueued back to back like sample passes.
+   ATR_E_INVALID: atr_render_start_samples' checks; sample_count == NULL; tolerance negative, NaN or
+   infinite; a variant other than AUTO or PATHS; bounce_limit > 64. */
+#define ATR_SAMPLES_CONVERGED 0x80000000u
+int atr_render_start_adaptive(atr_ctx* ctx, const atr_camera* cam, const atr_tile* tiles, int32_t ntiles,
+                              const atr_frame* frame, uint64_t seed, void* stream, int32_t variant,
+                              uint32_t first_sample, float* sample_sum, uint32_t* sample_count,
+                              float tolerance);
+/* The counts of the last adaptive pass enqueued on the context; valid once atr_render_wait
+   returned 0. info_out[0] pixels live at the start of the pass, [1] blocks with at least one live
+   pixel (the launch's 8x8 cells, or their row bands under a cell plan), [2] camera path groups
+   traced (64 consecutive paths of one block's live pixels), [3] pixels still live after the pass
+   ([0] minus the newly converged; 0 = further passes would do nothing). ATR_E_INVALID if the
+   context has enqueued no adaptive pass. */
+int atr_render_adaptive_info(atr_ctx* ctx, int64_t info_out[4]);
 /* Frames in flight in one launch (throughput, e.g. a live view rendering ahead): nframes renders
    of the same camera and tiles; frame f's outputs start frame_stride elements after frame f-1's
    (rgb: 3 x frame_stride floats; frame_stride >= the layout's pixels per frame). The cell
