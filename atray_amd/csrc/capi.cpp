@@ -27,6 +27,9 @@
 using namespace atr;
 
 extern "C" hipError_t atr_launch_render(const atr::RenderParams& P, int sched, int primary_occ, hipStream_t s);
+extern "C" int atr_render_reads_pads(const atr::RenderParams& P, int sched);
+extern "C" hipError_t atr_launch_camera_pads(const atr::DScene* scene, const atr::PadEyes& eyes, int32_t nrows,
+                                             int32_t stride, atr::float2_t* table, hipStream_t s);
 extern "C" hipError_t atr_launch_traced_finish(unsigned long long* slots, unsigned long long* out, hipStream_t s);
 extern "C" hipError_t atr_launch_unpack(const atr::DBlock* blocks, int32_t nblocks, int32_t width,
                                         const uint32_t* packed, uint32_t* image, hipStream_t s);
@@ -296,6 +299,28 @@ struct atr_ctx {
     static constexpr int kAdaptSlots = 8;
     unsigned long long* adapt_info = nullptr;
     int adapt_next = 0, adapt_last = -1;
+    // Tables of box growths for the primary kernels (RenderParams::pads): one row of
+    // {loose, tight} pairs per camera of a launch. A launch whose scene upload (scene_gen), row
+    // count and eyes (bit-equal) match a slot reads it as it is -- any number of launches in flight
+    // may share a table -- else it rebuilds the least recently used slot on its own stream, after a
+    // GPU-side wait for that slot's build and for the last launch on every stream that read it
+    // (`readers`: the slot's own events, never the traced-ray ring's). camera_pads: ATR_CAMERA_PADS
+    // at atr_create (0 = the kernels that compute the pairs inline).
+    struct PadSlot {
+        DevBuf mem;
+        uint64_t gen = 0;  // scene_gen of the table's scene; 0: empty
+        int32_t rows = 0;
+        float eye[kMaxFrameCams][3];
+        hipEvent_t built = nullptr;
+        hipStream_t built_on = nullptr;
+        std::vector<std::pair<hipStream_t, hipEvent_t>> readers;
+        uint64_t last_use = 0;
+    };
+    static constexpr int kPadSlots = 4;
+    static constexpr size_t kPadMaxBytes = size_t(256) << 20;  // larger tables: the inline kernels
+    PadSlot pad_slot[kPadSlots];
+    uint64_t pad_clock = 0, scene_gen = 0;
+    bool camera_pads = true;
 };
 
 namespace {
@@ -836,6 +861,78 @@ hipError_t launch_paths(atr_ctx* c, const RenderParams& P, hipStream_t s) {
 // An adaptive pass (`live`) is the path engine as one range, like a sample pass, and has no
 // fallback: hipErrorOutOfMemory goes back to the caller, returned by launch_paths_range before it
 // enqueues anything.
+// Bind a table of box growths to a launch that runs HYBRID's primary kernels (atr_ctx::PadSlot):
+// a cached table of the same scene and eyes, or the least recently used slot rebuilt on s ahead of
+// the render. *used = the slot the launch reads (launch_kernels records the launch in its readers),
+// or null with P.pads null: the kernels that compute the pairs inline (the switch is off, no
+// clusters, a table beyond kPadMaxBytes, or no memory for it -- the same output bits either way).
+hipError_t bind_pads(atr_ctx* c, RenderParams& P, int sched, hipStream_t s, atr_ctx::PadSlot** used) {
+    *used = nullptr;
+    P.pads = nullptr;
+    P.pads_stride = 0;
+    if (!c->camera_pads || c->nclusters <= 0 || c->nclusters > int64_t(1) << 30 || !atr_render_reads_pads(P, sched))
+        return hipSuccess;
+    const int32_t rows = P.nfcam > 0 ? P.nfcam : 1;
+    if (rows > kMaxFrameCams) return hipSuccess;
+    const int32_t stride = int32_t(c->nclusters);
+    const size_t bytes = size_t(rows) * size_t(stride) * sizeof(float2_t);
+    if (bytes > atr_ctx::kPadMaxBytes) return hipSuccess;
+    PadEyes eyes;
+    std::memset(&eyes, 0, sizeof(eyes));
+    for (int32_t f = 0; f < rows; ++f) {
+        const atr_vec3& e = P.nfcam > 0 ? P.fcam[f].eye : P.cam.eye;
+        eyes.e[f][0] = e.x, eyes.e[f][1] = e.y, eyes.e[f][2] = e.z;
+    }
+    hipError_t e;
+    atr_ctx::PadSlot* sl = nullptr;
+    atr_ctx::PadSlot* lru = &c->pad_slot[0];
+    for (atr_ctx::PadSlot& q : c->pad_slot) {
+        if (q.gen == c->scene_gen && q.rows == rows && std::memcmp(q.eye, eyes.e, sizeof(float) * 3 * size_t(rows)) == 0) {
+            sl = &q;
+            break;
+        }
+        if (q.last_use < lru->last_use) lru = &q;
+    }
+    if (sl) {  // cached: read it as it is, after its build when that ran on another stream
+        if (sl->built_on != s && (e = hipStreamWaitEvent(s, sl->built, 0)) != hipSuccess) return e;
+    } else {
+        sl = lru;
+        if (!sl->built && (e = hipEventCreateWithFlags(&sl->built, hipEventDisableTiming)) != hipSuccess) return e;
+        if (sl->mem.n < bytes || !sl->mem.p) {  // grow: nothing in flight may still touch the old buffer
+            if (sl->mem.p) {
+                if ((e = wait_list(sl->readers)) != hipSuccess) return e;
+                if ((e = hipEventSynchronize(sl->built)) != hipSuccess) return e;
+                (void)hipFree(sl->mem.p);
+            }
+            sl->mem = DevBuf();
+            sl->gen = 0;
+            if (hipMalloc(&sl->mem.p, bytes) != hipSuccess) {
+                (void)hipGetLastError();  // no memory for a table: the inline kernels
+                sl->mem = DevBuf();
+                return hipSuccess;
+            }
+            sl->mem.n = bytes;
+        } else {  // rewrite in place: after the slot's last build and its last reader on every stream
+            if (sl->gen && sl->built_on != s && (e = hipStreamWaitEvent(s, sl->built, 0)) != hipSuccess) return e;
+            for (const auto& se : sl->readers)
+                if (se.first != s && (e = hipStreamWaitEvent(s, se.second, 0)) != hipSuccess) return e;
+        }
+        sl->gen = 0;  // stays empty if the build cannot be enqueued
+        if ((e = atr_launch_camera_pads(c->d_scene, eyes, rows, stride, static_cast<float2_t*>(sl->mem.p), s)) != hipSuccess)
+            return e;
+        if ((e = hipEventRecord(sl->built, s)) != hipSuccess) return e;
+        sl->built_on = s;
+        sl->gen = c->scene_gen;
+        sl->rows = rows;
+        std::memcpy(sl->eye, eyes.e, sizeof(eyes.e));
+    }
+    sl->last_use = ++c->pad_clock;
+    P.pads = static_cast<const float2_t*>(sl->mem.p);
+    P.pads_stride = stride;
+    *used = sl;
+    return hipSuccess;
+}
+
 hipError_t launch_kernels(atr_ctx* c, RenderParams& P, int sched, hipStream_t s, const PathLive* live = nullptr) {
     if (live) return launch_paths_range(c, P, s, 0, P.nblocks, live);
     if (sched == kSchedPaths) {
@@ -848,7 +945,12 @@ hipError_t launch_kernels(atr_ctx* c, RenderParams& P, int sched, hipStream_t s,
         if (P.traced_rays && (e = hipMemsetAsync(P.traced_rays, 0, kTraceBytes, s)) != hipSuccess) return e;
         sched = sched_of(ATR_KERNEL_FLAT);
     }
-    return atr_launch_render(P, sched, c->tune.primary_occ, s);
+    atr_ctx::PadSlot* pads = nullptr;  // HYBRID's primaries read the cameras' table of box growths
+    hipError_t e = bind_pads(c, P, sched, s, &pads);
+    if (e != hipSuccess) return e;
+    e = atr_launch_render(P, sched, c->tune.primary_occ, s);
+    if (e == hipSuccess && pads) e = note_stream(pads->readers, s);
+    return e;
 }
 
 // Launch a render schedule; the traced rays go into a zeroed set of 64 spread counters from the
@@ -1124,6 +1226,9 @@ int atr_create(int device, atr_ctx** out) {
     atr_ctx* c = new (std::nothrow) atr_ctx();
     if (!c) return ATR_E_NOMEM;
     c->device = device;
+    // ATR_CAMERA_PADS=0: this context's primary kernels compute the box growths inline (A/B runs and
+    // the tests that compare the two); unset or anything else: they read the per-camera table
+    if (const char* v = std::getenv("ATR_CAMERA_PADS")) c->camera_pads = !(v[0] == '0' && v[1] == '\0');
     const int rc = [&]() -> int {  // any failure below releases what was created (atr_destroy)
         HIPCHK(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
         HIPCHK(hipEventCreate(&c->ev_start));
@@ -1199,6 +1304,11 @@ int atr_destroy(atr_ctx* c) {
         if (e) (void)hipEventDestroy(e);
     if (c->tring) (void)hipFree(c->tring);
     if (c->adapt_info) (void)hipFree(c->adapt_info);
+    for (atr_ctx::PadSlot& q : c->pad_slot) {
+        if (q.mem.p) (void)hipFree(q.mem.p);
+        if (q.built) (void)hipEventDestroy(q.built);
+        for (auto& se : q.readers) (void)hipEventDestroy(se.second);
+    }
     if (c->ev_start) (void)hipEventDestroy(c->ev_start);
     if (c->ev_stop) (void)hipEventDestroy(c->ev_stop);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -1233,6 +1343,7 @@ int atr_scene_upload(atr_ctx* c, const atr_material* mats, int32_t nmats, const 
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(wait_all(c));  // kernels on any stream may still read the old scene
     free_scene(c);
+    ++c->scene_gen;  // every table of box growths belongs to the old scene now
     DScene S;
     std::memset(&S, 0, sizeof(S));
     for (int32_t i = 0; i < nmats; ++i) {
@@ -1318,6 +1429,9 @@ int atr_scene_upload(atr_ctx* c, const atr_material* mats, int32_t nmats, const 
             dm.clus = clus;
             dm.cnrm = reinterpret_cast<const uint4_t*>(dm.clus + 2);
             if ((rc = up(PT.cl_range, dm.cl_range)) || (rc = up(PT.prim, dm.prim))) return rc;
+            if (c->nclusters + int64_t(PT.nclusters) > int64_t(UINT32_MAX)) return ATR_E_INVALID;
+            dm.cl_base = uint32_t(c->nclusters);  // the model's place in the scene-wide cluster numbering
+            dm.cl_count = uint32_t(PT.nclusters);
             c->nclusters += int64_t(PT.nclusters);
             if ((rc = up(PT.nodes, dm.nodes)) || (rc = up(PT.leaf_range, dm.leaf_range))) return rc;
             if (PT.tris.empty()) PT.tris.resize(1);

@@ -42,12 +42,15 @@ __device__ __forceinline__ void load_prim(const DModel& m, uint32_t k, float4_t&
 typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
 
 // Which scan flavours load the first screen normals with the box test (cluster_cands EARLY): bit 0
-// primary-only rays, bit 1 camera rays of the path engine, bit 2 bounce rays (experiment builds
-// set others; 0 = every flavour loads them after the box test passes). Not the camera rays: their
-// 6-wave kernel then spills 20 dwords instead of 5 and writes 4 GB more per c4 frame, for no time
-// measured (c4 3,824-3,826 Mrays/s without, 3,828-3,834 with)
+// primary-only rays, bit 1 camera rays of the path engine, bit 2 bounce rays, bit 3 primary-only
+// rays that read the per-camera table of box growths (experiment builds set others; 0 = every
+// flavour loads them after the box test passes). Not the camera rays: their 6-wave kernel then
+// spills 20 dwords instead of 5 and writes 4 GB more per c4 frame, for no time measured (c4
+// 3,824-3,826 Mrays/s without, 3,828-3,834 with). The table flavour keeps them although its 7-wave
+// kernel would have no scratch without: c3 8,851-8,952 Mrays/s with, 8,603-8,799 without
+// 
 #ifndef ATR_EARLY_NRM
-#define ATR_EARLY_NRM 5
+#define ATR_EARLY_NRM 13
 #endif
 
 // Ray-side constants of the cluster screen, once per ray (f16 direction, its L1 norm).
@@ -66,23 +69,35 @@ __device__ __forceinline__ ScreenRay screen_ray(const Ray& r) {
     return s;
 }
 
-// Cluster record lo = {lo.xyz, P | (n - 1)}, hi = {hi.xyz, q}: the two rounding-padded box
-// tests. False: no primitive inside can be accepted with t <= best. Else the det band
-// [dlo, dhi) of the primitives that still need the full test.
-__device__ __forceinline__ bool cluster_pads(const Ray& r, const ScreenRay& sr, float4_t lo, float4_t hi, float best,
-                                             float& dlo, float& dhi) {
+// The part of the padded box test that depends only on the ray origin and the cluster record
+// lo = {lo.xyz, P | (n - 1)}, hi = {hi.xyz, q}: the growths of the loose (x) and the tight (y) box.
+// Camera rays share one origin, so the primary kernels read this pair per (camera, cluster) from a
+// table (render.hip camera_pads_kernel) that calls this same function: the same operations in the
+// same order (-ffp-contract=off), the same bits as the inline evaluation.
+__device__ __forceinline__ float2_t cluster_grow(V3 o, float4_t lo, float4_t hi) {
     const float ex = hi.x - lo.x, ey = hi.y - lo.y, ez = hi.z - lo.z;
-    const float fx = fmaxf(fabsf(lo.x - r.o.x), fabsf(hi.x - r.o.x));
-    const float fy = fmaxf(fabsf(lo.y - r.o.y), fabsf(hi.y - r.o.y));
-    const float fz = fmaxf(fabsf(lo.z - r.o.z), fabsf(hi.z - r.o.z));
+    const float fx = fmaxf(fabsf(lo.x - o.x), fabsf(hi.x - o.x));
+    const float fy = fmaxf(fabsf(lo.y - o.y), fabsf(hi.y - o.y));
+    const float fz = fmaxf(fabsf(lo.z - o.z), fabsf(hi.z - o.z));
     // W >= |o - a| + |edge| for every primitive inside (far corner; L1 extent >= diagonal). The
     // hardware square root (v_sqrt_f32, within 1 ulp) instead of the correctly rounded expansion
     // (~15 VALU: denormal scaling, two FMA corrections): W only has to bound the distance from
     // above, the 1 + 2^-21 factor covers 8 ulp, and the 2^-63 term the flushed denormal case
     const float W = (__builtin_amdgcn_sqrtf(fx * fx + fy * fy + fz * fz) + 1.0842022e-19f) * 1.0000005f + (ex + ey + ez);
     const float P = lo.w;  // >= |ab||ac| of every primitive inside
-    const float gl = W * (P * (kPadRel / (0.9f * kTol)) + kPadAbs);
-    const float gt = W * (P * (kPadRel / (0.9f * kTau)) + kPadAbs);
+    float2_t g;
+    g.x = W * (P * (kPadRel / (0.9f * kTol)) + kPadAbs);
+    g.y = W * (P * (kPadRel / (0.9f * kTau)) + kPadAbs);
+    return g;
+}
+
+// Cluster record lo, hi and its growths g (cluster_grow): the two rounding-padded box
+// tests. False: no primitive inside can be accepted with t <= best. Else the det band
+// [dlo, dhi) of the primitives that still need the full test.
+__device__ __forceinline__ bool cluster_pads(const Ray& r, const ScreenRay& sr, float4_t lo, float4_t hi, float2_t g,
+                                             float best, float& dlo, float& dhi) {
+    const float gl = g.x, gt = g.y;
+    const float P = lo.w;
     // slab entry/exit of the unpadded box per axis, then widened by g |inv| per axis
     const float x0 = (lo.x - r.o.x) * r.inv.x, x1 = (hi.x - r.o.x) * r.inv.x;
     const float y0 = (lo.y - r.o.y) * r.inv.y, y1 = (hi.y - r.o.y) * r.inv.y;
@@ -164,9 +179,13 @@ __device__ __forceinline__ uint32_t screen8(const ScreenRay& sr, float blo, floa
 
 // Cluster c of a leaf: the padded box tests and the screen against the bound `best`. Returns the
 // mask of the primitives (slot 16 c + bit) that still need the full test.
-template <bool COUNT, bool EARLY = true>
+// PADS: the growths of the box come from the camera's table row `pads` (indexed by the model's
+// cluster), loaded with the cluster record, instead of being computed from the origin.
+template <bool COUNT, bool EARLY = true, bool PADS = false>
 __device__ __forceinline__ uint32_t cluster_cands(const Ray& r, const DModel& m, uint32_t c, float4_t lo, float4_t hi,
-                                                  float best, Ctr& ct) {
+                                                  float best, Ctr& ct, const float2_t* pads = nullptr) {
+    float2_t g;
+    if constexpr (PADS) g = pads[c];
     // the screen constants (7 values) are recomputed for every cluster from an opaque copy of the
     // ray instead of being hoisted out of the scan loops and held through the passes and rounds:
     // ~10 VALU per cluster for 7 VGPRs, what lets HYBRID run 6 waves/SIMD
@@ -181,8 +200,9 @@ __device__ __forceinline__ uint32_t cluster_cands(const Ray& r, const DModel& m,
     if constexpr (EARLY) {
         e0 = nb[0], e1 = nb[1], ez = nb[kMaxClusterSize / 4];
     }
+    if constexpr (!PADS) g = cluster_grow(r.o, lo, hi);
     float dlo, dhi;
-    if (!cluster_pads(r, sr, lo, hi, best, dlo, dhi)) return 0;
+    if (!cluster_pads(r, sr, lo, hi, g, best, dlo, dhi)) return 0;
     const uint32_t n = (__float_as_uint(lo.w) & 31u) + 1u;
     if constexpr (COUNT) ct.screen += n;
     const uint32_t slots = (2u << (n - 1)) - 1u;  // [0, n), 1 <= n <= 16

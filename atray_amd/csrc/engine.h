@@ -138,6 +138,9 @@ struct DModel {
     int32_t smooth;              // normals.size > 0 (renderer.cpp:129)
     int32_t material;
     float aabb[6];               // Model::surrounding_aabb
+    // the model's clusters in the scene-wide cluster numbering (the tree models' clusters in model
+    // order): the index of the per-camera table of box growths (RenderParams::pads)
+    uint32_t cl_base, cl_count;
 };
 
 struct DMaterial { float ex, ey, ez, rx, ry, rz, scatter, pad; };
@@ -205,6 +208,17 @@ struct RenderParams {
     // other kernel's code is what it was without them.
     uint32_t first_sample;
     float* sample_sum;     // non-null -> an accumulating pass
+    // The primary kernels' table of box growths (cluster.h cluster_grow): row f --
+    // frame f's camera (row 0 alone without per-frame cameras) -- holds one {loose, tight} pair per
+    // cluster of the scene, pads_stride pairs per row. Non-null selects the primary kernels that
+    // read it; after the fields above, and read by those kernels only.
+    const float2_t* pads;
+    int32_t pads_stride;
+};
+
+// The eyes of a launch's cameras, by value, for the kernel that fills the table.
+struct PadEyes {
+    float e[kMaxFrameCams][3];
 };
 
 // Sample-parallel path engine (paths.hip): one lane per (pixel, sample) path. A batch

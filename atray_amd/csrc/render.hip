@@ -111,9 +111,14 @@ __device__ __forceinline__ V3 cast_ray(const DScene* __restrict__ S, V3 o, V3 d,
 // (P.sample_sum, the f32 sum of samples [0, first_sample) in sample order) and go back there, and the
 // mean is over first_sample + spp samples -- the f32 adds of a one-shot render of that many samples,
 // in its order. The primary hit outputs belong to the frame's sample 0.
-template <int SCHED, bool COUNT, bool PRIMARY, int OCC = 4, bool ACCUM = false>
+//
+// PADS (HYBRID primaries): the clusters' box growths, which depend on the camera eye and the cluster
+// alone, come from the launch's table P.pads (camera_pads_kernel below) instead of being computed
+// per (ray, cluster): the same values, bit for bit (cluster.h cluster_grow).
+template <int SCHED, bool COUNT, bool PRIMARY, int OCC = 4, bool ACCUM = false, bool PADS = false>
 __global__ __launch_bounds__(256, OCC) void render_kernel(RenderParams P) {
     static_assert(!ACCUM || (SCHED == SCHED_FLAT && !PRIMARY && !COUNT), "sample passes run on FLAT");
+    static_assert(!PADS || (SCHED == SCHED_HYBRID && PRIMARY), "the table serves HYBRID's primary flavour");
     // the wave index is uniform: in an SGPR, so are the cell and frame indices derived from it
     const int wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6)), lane = threadIdx.x & 63;
     const int b = remap_xcd(blockIdx.x, gridDim.x, P.xcd_chunk) * 4 + wave;
@@ -165,7 +170,14 @@ __global__ __launch_bounds__(256, OCC) void render_kernel(RenderParams P) {
     if constexpr (PRIMARY) {
         Isect id;
         id.type = T_NONE;
-        intersect_scene<SCHED, FLAV_PRIMARY, COUNT>(S, eye, dir, active, id, err, ct, P.hyb_a, P.hyb_b);
+        if constexpr (PADS) {
+            // the camera's row: the frame index and the stride are wave-uniform, the base stays in SGPRs
+            const int32_t row = P.nfcam > 0 ? __builtin_amdgcn_readfirstlane(fidx) : 0;
+            const float2_t* pads = uniform_global(P.pads) + int64_t(row) * P.pads_stride;
+            intersect_scene<SCHED, FLAV_PRIMARY_PADS, COUNT>(S, eye, dir, active, id, err, ct, P.hyb_a, P.hyb_b, pads);
+        } else {
+            intersect_scene<SCHED, FLAV_PRIMARY, COUNT>(S, eye, dir, active, id, err, ct, P.hyb_a, P.hyb_b);
+        }
         if (active) {
             const DMaterial& mat = S->mats[id.material];
             col = add(col, mk(mat.ex, mat.ey, mat.ez));  // ret = (0 + (1,1,1) x emission)
@@ -294,7 +306,8 @@ __global__ __launch_bounds__(256, OCC) void render_kernel(RenderParams P) {
 
 // The shipping instantiations (12): LANE {count} x {primary} + the 5-wave primary; HYBRID primaries
 // at 6 (one frame) / 7 (frames in flight) waves/SIMD, its bounce-loop build and the COUNT builds;
-// FLAT at 6 / 7 waves/SIMD and its COUNT build. Plus FLAT's ACCUM flavour (sample passes).
+// FLAT at 6 / 7 waves/SIMD and its COUNT build. Plus FLAT's ACCUM flavour (sample passes) and the
+// PADS builds of HYBRID's primaries (the per-camera table of box growths), below.
 template __global__ void render_kernel<SCHED_LANE, false, false>(RenderParams);
 template __global__ void render_kernel<SCHED_LANE, true, false>(RenderParams);
 template __global__ void render_kernel<SCHED_LANE, true, true>(RenderParams);
@@ -310,6 +323,31 @@ template __global__ void render_kernel<SCHED_FLAT, false, false, 7>(RenderParams
 template __global__ void render_kernel<SCHED_FLAT, true, false>(RenderParams);
 // and the sample passes' FLAT kernel (atr_render_start_samples)
 template __global__ void render_kernel<SCHED_FLAT, false, false, 6, true>(RenderParams);
+// and HYBRID's primaries reading the per-camera table of box growths (PADS), with their COUNT build
+template __global__ void render_kernel<SCHED_HYBRID, false, true, 6, false, true>(RenderParams);
+template __global__ void render_kernel<SCHED_HYBRID, false, true, 7, false, true>(RenderParams);
+template __global__ void render_kernel<SCHED_HYBRID, false, true, 8, false, true>(RenderParams);
+template __global__ void render_kernel<SCHED_HYBRID, true, true, 4, false, true>(RenderParams);
+
+// The table of box growths (RenderParams::pads): thread (x, y) computes the pair of scene cluster x
+// for camera y's eye -- cluster_grow, the function the inline path evaluates per (ray, cluster) --
+// and writes table[y * stride + x]. stride = the scene's cluster count (DModel::cl_base / cl_count).
+__global__ __launch_bounds__(256) void camera_pads_kernel(const DScene* __restrict__ S, PadEyes eyes, int32_t stride,
+                                                          float2_t* __restrict__ table) {
+    const uint32_t x = blockIdx.x * 256u + threadIdx.x;
+    if (x >= uint32_t(stride)) return;
+    const int32_t f = __builtin_amdgcn_readfirstlane(int32_t(blockIdx.y));
+    const V3 eye = mk(eyes.e[f][0], eyes.e[f][1], eyes.e[f][2]);
+    const int32_t nmodels = S->nmodels;
+    for (int32_t i = 0; i < nmodels; ++i) {
+        const DModel& m = S->models[i];
+        const uint32_t c = x - m.cl_base;  // wraps below the model's first cluster
+        if (!m.has_tree || c >= m.cl_count) continue;
+        table[size_t(f) * size_t(stride) + x] =
+            cluster_grow(eye, m.clus[kClusterBlock * size_t(c)], m.clus[kClusterBlock * size_t(c) + 1]);
+        return;
+    }
+}
 
 // Sum the 64 traced-ray counters of a launch into the caller's accumulator and clear them.
 __global__ __launch_bounds__(64) void traced_finish_kernel(unsigned long long* __restrict__ slots,
@@ -383,10 +421,44 @@ __global__ __launch_bounds__(256) void packed_tile_casts_kernel(const int32_t* _
 }  // namespace atr
 
 // ------------------------------------------------------------------ launchers used by capi.cpp
-template <int SC, bool C, bool PR, int OCC = 4, bool ACCUM = false>
+template <int SC, bool C, bool PR, int OCC = 4, bool ACCUM = false, bool PADS = false>
 static void launch_one(const atr::RenderParams& P, hipStream_t s) {
     const int grid = (P.nblocks + 3) / 4;
-    hipLaunchKernelGGL((atr::render_kernel<SC, C, PR, OCC, ACCUM>), dim3(grid), dim3(256), 0, s, P);
+    hipLaunchKernelGGL((atr::render_kernel<SC, C, PR, OCC, ACCUM, PADS>), dim3(grid), dim3(256), 0, s, P);
+}
+
+// HYBRID's primary kernel at `occ` waves/SIMD (0: the COUNT build), reading P.pads when it is set.
+static void launch_hybrid_primary(const atr::RenderParams& P, int occ, hipStream_t s) {
+    using namespace atr;
+    if (P.pads) {
+        if (occ == 0) launch_one<SCHED_HYBRID, true, true, 4, false, true>(P, s);
+        else if (occ == 8) launch_one<SCHED_HYBRID, false, true, 8, false, true>(P, s);
+        else if (occ == 7) launch_one<SCHED_HYBRID, false, true, 7, false, true>(P, s);
+        else launch_one<SCHED_HYBRID, false, true, 6, false, true>(P, s);
+    } else {
+        if (occ == 0) launch_one<SCHED_HYBRID, true, true>(P, s);
+        else if (occ == 8) launch_one<SCHED_HYBRID, false, true, 8>(P, s);
+        else if (occ == 7) launch_one<SCHED_HYBRID, false, true, 7>(P, s);
+        else launch_one<SCHED_HYBRID, false, true, 6>(P, s);
+    }
+}
+
+// True when atr_launch_render would run one of HYBRID's primary kernels for P: the launches that
+// can read a table of box growths (capi.cpp binds one to P.pads before the launch).
+extern "C" int atr_render_reads_pads(const atr::RenderParams& P, int sched) {
+    using namespace atr;
+    const bool prim = P.cam.bounce_limit == 1 && !P.cam.anti_aliasing && P.cam.samples_per_pixel == 1;
+    return prim && !P.sample_sum && (sched == SCHED_HYBRID || sched == SCHED_FLAT);
+}
+
+// Fill rows [0, nrows) of a table of box growths for the scene's `stride` clusters (camera_pads_kernel).
+extern "C" hipError_t atr_launch_camera_pads(const atr::DScene* scene, const atr::PadEyes& eyes, int32_t nrows,
+                                             int32_t stride, atr::float2_t* table, hipStream_t s) {
+    if (nrows <= 0 || stride <= 0) return hipSuccess;
+    if (nrows > atr::kMaxFrameCams) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(atr::camera_pads_kernel, dim3(unsigned((stride + 255) / 256), unsigned(nrows)), dim3(256), 0, s,
+                       scene, eyes, stride, table);
+    return hipGetLastError();
 }
 
 // sched: 0 LANE, 6 FLAT, 7 HYBRID (capi.cpp sched_of). Occupancy per schedule and launch shape by
@@ -411,15 +483,13 @@ extern "C" hipError_t atr_launch_render(const atr::RenderParams& P, int sched, i
     const bool prim8 = occ == 8;
     switch (sched) {
         case SCHED_HYBRID:
-            if (count) { if (prim) launch_one<SCHED_HYBRID, true, true>(P, s); else launch_one<SCHED_HYBRID, true, false>(P, s); }
+            if (count) { if (prim) launch_hybrid_primary(P, 0, s); else launch_one<SCHED_HYBRID, true, false>(P, s); }
             else if (!prim) launch_one<SCHED_HYBRID, false, false>(P, s);  // LDS: 4 workgroups per CU
-            else if (prim8) launch_one<SCHED_HYBRID, false, true, 8>(P, s);
-            else if (prim7) launch_one<SCHED_HYBRID, false, true, 7>(P, s);
-            else launch_one<SCHED_HYBRID, false, true, 6>(P, s);
+            else launch_hybrid_primary(P, prim8 ? 8 : prim7 ? 7 : 6, s);
             break;
         case SCHED_FLAT:
-            if (prim && !count) launch_one<SCHED_HYBRID, false, true, 6>(P, s);  // primaries: HYBRID's kernel
-            else if (count) { if (prim) launch_one<SCHED_HYBRID, true, true>(P, s); else launch_one<SCHED_FLAT, true, false>(P, s); }
+            if (prim && !count) launch_hybrid_primary(P, 6, s);  // primaries: HYBRID's kernel
+            else if (count) { if (prim) launch_hybrid_primary(P, 0, s); else launch_one<SCHED_FLAT, true, false>(P, s); }
             else if (multi) launch_one<SCHED_FLAT, false, false, 7>(P, s);
             else launch_one<SCHED_FLAT, false, false, 6>(P, s);
             break;

@@ -401,12 +401,15 @@ __device__ __forceinline__ void flat_pass(const Ray& r, const DModel& m, int w, 
 // the visiting order (minimum (t, leaf rank)), so the choice changes no output bit. Then each live
 // lane stops at the first leaf that improved its hit (kd_tree.cpp:457-460), moves to its next
 // leaf, or asks for a re-walk. UO: one origin for the whole wave. NUV: u and v feed no output.
-template <bool COUNT, bool HYB, bool UO, bool NUV, int K = kLeafBuf>
+// PADS: the box growths of each cluster come from `pads`, the camera's row of the per-camera table
+// at this model's first cluster (cluster.h cluster_grow; primary flavour only, wave-uniform).
+template <bool COUNT, bool HYB, bool UO, bool NUV, int K = kLeafBuf, bool PADS = false>
 __device__ __forceinline__ void flat_leaf_step(const Ray& r, const DModel& m, int w, int ln, bool live, FlatQ& q,
-                                               Ctr& ct, int32_t hyb_a, int32_t hyb_b) {
+                                               Ctr& ct, int32_t hyb_a, int32_t hyb_b, const float2_t* pads = nullptr) {
+    static_assert(!PADS || UO, "the table holds one origin per camera");
     FlatLds<K, !NUV>& L = flat_lds<K, !NUV>();
     // flavour of the scan (primary-only, camera, bounce rays) -> early screen normals (cluster.h)
-    constexpr bool kEarly = ((NUV ? 1 : UO ? 2 : 4) & ATR_EARLY_NRM) != 0;
+    constexpr bool kEarly = ((PADS ? 8 : NUV ? 1 : UO ? 2 : 4) & ATR_EARLY_NRM) != 0;
     ATR_PCLK(const uint64_t tc2 = clock64());
     uint32_t cf = 0, cn = 0;
     if (live) {
@@ -435,8 +438,8 @@ __device__ __forceinline__ void flat_leaf_step(const Ray& r, const DModel& m, in
             if (i < cn) {
                 const uint32_t c = cf + i;
                 const float bound = __uint_as_float(uint32_t(L.key[w][ln] >> 32));
-                cm = cluster_cands<COUNT, kEarly>(r, m, c, m.clus[kClusterBlock * size_t(c)],
-                                          m.clus[kClusterBlock * size_t(c) + 1], bound, ct);
+                cm = cluster_cands<COUNT, kEarly, PADS>(r, m, c, m.clus[kClusterBlock * size_t(c)],
+                                                m.clus[kClusterBlock * size_t(c) + 1], bound, ct, pads);
             }
             cand_rounds<COUNT, UO, NUV, true, K>(r, m, w, ln, cm, kMaxClusterSize * (cf + i), ln, ct);
         }
@@ -466,8 +469,8 @@ __device__ __forceinline__ void flat_leaf_step(const Ray& r, const DModel& m, in
         uint32_t cm = 0;
         if (valid) {
             const float bound = __uint_as_float(uint32_t(L.key[w][own] >> 32));
-            cm = cluster_cands<COUNT, kEarly>(qr, m, c, m.clus[kClusterBlock * size_t(c)], m.clus[kClusterBlock * size_t(c) + 1],
-                                      bound, ct);
+            cm = cluster_cands<COUNT, kEarly, PADS>(qr, m, c, m.clus[kClusterBlock * size_t(c)],
+                                                    m.clus[kClusterBlock * size_t(c) + 1], bound, ct, pads);
         }
         cand_rounds<COUNT, UO, NUV, false, K>(r, m, w, ln, cm, kMaxClusterSize * c, own, ct);
     }
@@ -504,9 +507,10 @@ __device__ __forceinline__ void flat_result(const DModel& m, bool active, int w,
 // One tree query of every active lane of the wave (called by all 64 lanes, converged): passes and
 // leaf steps until every lane's query is done. Flags as above.
 template <bool COUNT, bool HYB = false, bool LDSB = false, bool UO = false, bool UT = false, bool NUV = false,
-          bool NEAR = false, int K = kLeafBuf>
+          bool NEAR = false, int K = kLeafBuf, bool PADS = false>
 __device__ __forceinline__ void tree_closest_flat(const Ray& r, const DModel& m, bool active, Hit& h, int& err,
-                                                  Ctr& ct, int32_t hyb_a = 0, int32_t hyb_b = 0) {
+                                                  Ctr& ct, int32_t hyb_a = 0, int32_t hyb_b = 0,
+                                                  const float2_t* pads = nullptr) {
     const int w = threadIdx.x >> 6, ln = threadIdx.x & 63;
     ATR_PCLK(uint64_t tcs = clock64());
     FlatQ q = flat_begin<COUNT, K, !NUV>(r, m, active, w, ln, ct);
@@ -515,7 +519,7 @@ __device__ __forceinline__ void tree_closest_flat(const Ray& r, const DModel& m,
         flat_pass<COUNT, LDSB, UT, NEAR, K, !NUV>(r, m, w, ln, q, err, ct);
         ATR_PCLK(ct.t_pass += uint32_t(clock64() - tc0));
         if (__ballot(!q.done) == 0) break;
-        flat_leaf_step<COUNT, HYB, UO, NUV, K>(r, m, w, ln, !q.done, q, ct, hyb_a, hyb_b);
+        flat_leaf_step<COUNT, HYB, UO, NUV, K, PADS>(r, m, w, ln, !q.done, q, ct, hyb_a, hyb_b, pads);
     }
     flat_result<NUV, K>(m, active, w, ln, h);
     ATR_PCLK(ct.t_scan += uint32_t(clock64() - tcs));
@@ -525,8 +529,9 @@ __device__ __forceinline__ void tree_closest_flat(const Ray& r, const DModel& m,
 enum { SCHED_LANE = 0, SCHED_FLAT = 6, SCHED_HYBRID = 7 };
 // Flavours of the clustered scan: CAMERA rays (one origin, coherent: HYBRID's wave-walked passes,
 // LDS leaf buffer), BOUNCE rays (incoherent: dealt rounds, register leaf buffer), PRIMARY-only
-// frames (CAMERA without u and v).
-enum { FLAV_CAMERA = 0, FLAV_BOUNCE = 1, FLAV_PRIMARY = 2, FLAV_HYB_BOUNCE = 3 };
+// frames (CAMERA without u and v); PRIMARY_PADS: PRIMARY with the clusters' box growths read from
+// the per-camera table (cluster.h cluster_grow).
+enum { FLAV_CAMERA = 0, FLAV_BOUNCE = 1, FLAV_PRIMARY = 2, FLAV_HYB_BOUNCE = 3, FLAV_PRIMARY_PADS = 4 };
 #ifndef ATR_BOUNCE_HYB  // experiment builds: 1 = the path engine's bounce rays choose lane-private or
 #define ATR_BOUNCE_HYB 0  // dealt leaf steps per step as HYBRID does (thresholds hybrid_a, hybrid_b)
 #endif
@@ -562,10 +567,12 @@ struct SceneHit {
 // lanes take part in the wave-wide scans). SCHED_LANE: per-lane reference scan; otherwise the
 // clustered scan in flavour FLAV. intersect_models is the models' part; scene_finish (shade.h) the
 // spheres, planes and hit record, so a caller can re-read o and d between the two instead of
-// holding them through the query.
+// holding them through the query. pads (FLAV_PRIMARY_PADS): the camera's row of the table of box
+// growths, one pair per cluster of the scene (model i's from cl_base on); wave-uniform.
 template <int SCHED, int FLAV, bool COUNT, int KB = kLeafBuf>
 __device__ __forceinline__ SceneHit intersect_models(const DScene* __restrict__ S, V3 o, V3 d, bool active, int& err,
-                                                    Ctr& ct, int32_t hyb_a, int32_t hyb_b) {
+                                                    Ctr& ct, int32_t hyb_a, int32_t hyb_b,
+                                                    const float2_t* pads = nullptr) {
     const Ray r = make_ray(o, d);  // renderer.cpp:41-44
     SceneHit sh{kMaxFloat, 0.f, 0.f, 0u, -1};
     const int32_t nmodels = __builtin_amdgcn_readfirstlane(S->nmodels);  // uniform: an SGPR, not a VGPR
@@ -580,6 +587,9 @@ __device__ __forceinline__ SceneHit intersect_models(const DScene* __restrict__ 
                 tree_closest_flat<COUNT, true, true, true, true, false>(r, m, active, h, err, ct, hyb_a, hyb_b);
             else if constexpr (FLAV == FLAV_PRIMARY)
                 tree_closest_flat<COUNT, true, true, true, true, true>(r, m, active, h, err, ct, hyb_a, hyb_b);
+            else if constexpr (FLAV == FLAV_PRIMARY_PADS)
+                tree_closest_flat<COUNT, true, true, true, true, true, false, kLeafBuf, true>(
+                    r, m, active, h, err, ct, hyb_a, hyb_b, pads + __builtin_amdgcn_readfirstlane(m.cl_base));
             else if constexpr (FLAV == FLAV_HYB_BOUNCE)
                 tree_closest_flat<COUNT, true, false, false, false, false>(r, m, active, h, err, ct, hyb_a, hyb_b);
             else  // bounce rays: near-first passes into the LDS leaf buffer, every step dealt
@@ -605,8 +615,9 @@ __device__ __forceinline__ SceneHit intersect_models(const DScene* __restrict__ 
 
 template <int SCHED, int FLAV, bool COUNT>
 __device__ __forceinline__ void intersect_scene(const DScene* __restrict__ S, V3 o, V3 d, bool active, Isect& id,
-                                                int& err, Ctr& ct, int32_t hyb_a, int32_t hyb_b) {
-    const SceneHit sh = intersect_models<SCHED, FLAV, COUNT>(S, o, d, active, err, ct, hyb_a, hyb_b);
+                                                int& err, Ctr& ct, int32_t hyb_a, int32_t hyb_b,
+                                                const float2_t* pads = nullptr) {
+    const SceneHit sh = intersect_models<SCHED, FLAV, COUNT>(S, o, d, active, err, ct, hyb_a, hyb_b, pads);
     if (!active) return;
     scene_finish(S, o, d, sh.best, sh.face, sh.fu, sh.fv, sh.nm, id);  // :86-160
 }

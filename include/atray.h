@@ -149,6 +149,9 @@ int atr_write_bmp(const uint32_t* pixels, int32_t width, int32_t height, const c
 
 /* ---------------------------------------------------------------- device engine */
 typedef struct atr_ctx atr_ctx;
+/* atr_create reads one environment variable, for A/B runs: ATR_CAMERA_PADS=0 makes this context's
+   primary-only kernels compute each cluster's box growths per ray instead of reading them from the
+   per-camera table; unset or any other value: the table. Same output bits either way. */
 int atr_create(int device, atr_ctx** out);
 int atr_destroy(atr_ctx* ctx);
 const char* atr_version(void);
