@@ -163,8 +163,9 @@ class Camera:
 
 
 class Scene:
-    """One-model scene as the app builds it (app.cpp:65-146): load OBJ, surrounding AABB,
-    translate_to(center), SAH octree with leaf size ``max_faces`` (or brute force)."""
+    """A scene as the app builds it (app.cpp:65-146). The constructor makes a one-model scene:
+    load OBJ, surrounding AABB, translate_to(center), SAH octree with leaf size ``max_faces`` (or
+    brute force). ``Scene.compose`` puts several such models into one scene."""
 
     def __init__(self, obj_path=None, obj_text=None, center=(0.0, -15.0, -38.0), max_faces=300,
                  use_tree=True, materials=(SKY, MODEL_MAT), model_material=1, spheres=(),
@@ -200,8 +201,35 @@ class Scene:
             *[om_plane(_v(n), float(d), int(m)) for n, d, m in planes])
         self.s = om_scene(self._mats, len(materials), C.pointer(self._model), 1,
                           self._spheres, len(spheres), self._planes, len(planes))
+        self.parts = ()
 
-    # ---- introspection ------------------------------------------------------------
+    @classmethod
+    def compose(cls, parts, materials=(SKY, MODEL_MAT), spheres=(), planes=()):
+        """A scene of several models (app.cpp's scene.models, any number of them): ``parts`` are
+        loaded one-model scenes, in model order; each contributes its mesh, its tree (or brute
+        force) and its ``model_material``, which indexes ``materials`` here. The parts' own
+        materials, spheres and planes are not used. A part may appear more than once. The composed
+        scene holds its parts, which own the meshes and trees; ``primary_hits``, ``render``,
+        ``trace`` and the threaded renders work as for one model (face indices are per model)."""
+        self = cls.__new__(cls)
+        self.parts = tuple(parts)
+        self.mesh = self.tree = None
+        self._mats = (om_material * len(materials))(
+            *[om_material(_v(e), _v(r), float(s)) for e, r, s in materials])
+        self._models = (om_model * max(1, len(self.parts)))()
+        for i, p in enumerate(self.parts):
+            if p.mesh is None:
+                raise ValueError("compose: a part must be a one-model scene")
+            C.memmove(C.byref(self._models[i]), C.byref(p._model), C.sizeof(om_model))
+        self._spheres = (om_sphere * max(1, len(spheres)))(
+            *[om_sphere(_v(c), float(r), int(m)) for c, r, m in spheres])
+        self._planes = (om_plane * max(1, len(planes)))(
+            *[om_plane(_v(n), float(d), int(m)) for n, d, m in planes])
+        self.s = om_scene(self._mats, len(materials), self._models, len(self.parts),
+                          self._spheres, len(spheres), self._planes, len(planes))
+        return self
+
+    # ---- introspection (one-model scenes) ------------------------------------------------------------
     def mesh_arrays(self):
         m = self.mesh
         V = np.ctypeslib.as_array(C.cast(m.vertices, C.POINTER(C.c_float)), (m.nv * 3,)).reshape(-1, 3).copy() if m.nv else np.zeros((0, 3), np.float32)
@@ -290,6 +318,8 @@ class Scene:
 
     def __del__(self):
         try:
+            if self.mesh is None:  # composed: the parts free their own meshes and trees
+                return
             L = lib()
             if self.tree is not None:
                 L.om_free_tree(C.byref(self.tree))
