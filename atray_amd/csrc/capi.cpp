@@ -2245,8 +2245,10 @@ int atr_unpack_masked_ranks(atr_ctx* c, int32_t nsrc, const atr_tile* const* til
         }
         HIPCHK(atr_launch_unpack_masked_multi(n, blocks.data(), nb.data(), own.data(), packed + i0,
                                               raw ? raw + i0 : nullptr, width, nframes, image, image_stride, s));
+        // recorded per batch: a cache miss of the next batch may evict one of this batch's sets,
+        // and its wait_all has to cover this decode before the copy rewrites the blocks
+        HIPCHK(note_launch(c, s));
     }
-    HIPCHK(note_launch(c, s));
     return ATR_OK;
 }
 

@@ -408,14 +408,18 @@ int atr_scatter_bgr_masked(atr_ctx* ctx, const uint8_t* packed, int64_t npixels,
 /* The masked stream of a PACKED render of these tiles (nframes frames, as atr_pack_bgr_masked wrote
    it from that render's framebuffer) straight into IMAGE frames: frame f's pixel (x, y) at
    image[f * image_stride + y * width + x]. Positions come from the tile list's 8x8 blocks (as
-   atr_unpack) instead of an index per pixel: ~5 B of traffic per pixel instead of ~13. */
+   atr_unpack) instead of an index per pixel: ~5 B of traffic per pixel instead of ~13. The encoded
+   frames must be contiguous (the render's frame_stride == its packed pixels, atr_render_packed_size):
+   with `own` packed pixels per frame, stream pixel f * own + slot is frame f's packed slot. */
 int atr_unpack_masked(atr_ctx* ctx, const atr_tile* tiles, int32_t ntiles, int32_t width, int32_t height,
                       const uint8_t* packed, int32_t nframes, uint32_t* image, int64_t image_stride, void* stream);
 /* Several masked streams into the same IMAGE frames in one call (rank 0's received shards, one
    source per rank): source i is the PACKED render of tiles[i] (ntiles[i] tiles, the list it was
    rendered with), its stream at packed[i] (device), nframes frames each, image_stride apart; with
    raw[i] nonzero (raw may be NULL) packed[i] is that render's u32 PACKED framebuffer itself (rank
-   0's own frames), copied in by the same launch. The same pixels as atr_unpack_masked (or
+   0's own frames), copied in by the same launch. Either way a source's frames are contiguous
+   (frame_stride == its packed pixels: frame f's slot k is pixel, or u32, f * own + k of
+   packed[i]). The same pixels as atr_unpack_masked (or
    atr_unpack) per source, from one decode launch per 16 sources instead of a launch and an event
    per source. Asynchronous on `stream`. */
 int atr_unpack_masked_ranks(atr_ctx* ctx, int32_t nsrc, const atr_tile* const* tiles, const int32_t* ntiles,
