@@ -321,6 +321,8 @@ struct atr_ctx {
     PadSlot pad_slot[kPadSlots];
     uint64_t pad_clock = 0, scene_gen = 0;
     bool camera_pads = true;
+    // ATR_WAVE_CULL at atr_create (0 = the primary kernels test every cluster of a leaf per ray)
+    bool wave_cull = true;
 };
 
 namespace {
@@ -331,6 +333,7 @@ void apply_tuning(const atr_ctx* c, RenderParams& P) {
     P.frame_rotate = 0;
     P.hyb_a = c->tune.hybrid_a;
     P.hyb_b = c->tune.hybrid_b;
+    P.wave_cull = c->wave_cull ? 1 : 0;
 }
 
 int dev_upload(atr_ctx* c, const void* src, size_t bytes, void** out) {
@@ -1229,6 +1232,9 @@ int atr_create(int device, atr_ctx** out) {
     // ATR_CAMERA_PADS=0: this context's primary kernels compute the box growths inline (A/B runs and
     // the tests that compare the two); unset or anything else: they read the per-camera table
     if (const char* v = std::getenv("ATR_CAMERA_PADS")) c->camera_pads = !(v[0] == '0' && v[1] == '\0');
+    // ATR_WAVE_CULL=0: this context's primary kernels skip the wave cull of a leaf's clusters (A/B runs
+    // and the tests that compare the two); unset or anything else: they cull
+    if (const char* v = std::getenv("ATR_WAVE_CULL")) c->wave_cull = !(v[0] == '0' && v[1] == '\0');
     const int rc = [&]() -> int {  // any failure below releases what was created (atr_destroy)
         HIPCHK(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
         HIPCHK(hipEventCreate(&c->ev_start));
@@ -1867,6 +1873,20 @@ int atr_render_counters(atr_ctx* c, const atr_camera* cam, const atr_tile* tiles
     const int rc = count_launch(c, cam, tiles, ntiles, seed, variant, h);
     if (rc != ATR_OK) return rc;
     for (int k = 0; k < 10; ++k) out[k] = int64_t(h[k]);
+    return ATR_OK;
+}
+
+int atr_render_cull_counters(atr_ctx* c, const atr_camera* cam, const atr_tile* tiles, int32_t ntiles,
+                             uint64_t seed, int32_t variant, int64_t out[5]) {
+    if (!out) return ATR_E_INVALID;
+    unsigned long long h[kCounterSlots];
+    const int rc = count_launch(c, cam, tiles, ntiles, seed, variant, h);
+    if (rc != ATR_OK) return rc;
+    out[4] = int64_t(h[29]);  // cluster tests run per ray (lane level)
+    out[0] = int64_t(h[27]);  // (wave, cluster) pairs culled against the direction hull
+    out[1] = int64_t(h[28]);  // wave-level iterations of the lane-private cluster loop
+    out[2] = int64_t(h[25]);  // dealt rounds
+    out[3] = int64_t(h[26]);  // dealt items
     return ATR_OK;
 }
 

@@ -124,6 +124,35 @@ __device__ __forceinline__ bool cluster_pads(const Ray& r, const ScreenRay& sr, 
     return true;
 }
 
+// The direction hull of a wave of one-origin rays: per axis the smallest and the largest r.inv of
+// its lanes (wave-uniform: SGPRs). ok: all six are finite and an axis' two ends have one sign.
+struct WaveHull {
+    float lx, hx, ly, hy, lz, hz;
+    bool ok;
+};
+
+// The loose test of cluster_pads on the hull instead of one ray (the wave cull):
+// false only when cluster_pads returns false in every lane of the wave, whatever its best. The same
+// f32 operations on the interval's ends: lo - o and hi - o are the lanes' own bits (one origin),
+// fl(a s) is monotone in s, so is fl(g |s|) for g >= 0, fl(x - y) and fl(x + y) in each argument,
+// min and max; so every lane's tn is at least the lower tn here and its tf at most the upper tf.
+// Any NaN keeps the cluster (the comparisons are false), and so does a growth that overflows.
+__device__ __forceinline__ bool cluster_hull_keep(V3 o, const WaveHull& hl, float4_t lo, float4_t hi, float gl) {
+    const float ax = lo.x - o.x, bx = hi.x - o.x, ay = lo.y - o.y, by = hi.y - o.y, az = lo.z - o.z, bz = hi.z - o.z;
+    const float x0 = ax * hl.lx, x1 = ax * hl.hx, x2 = bx * hl.lx, x3 = bx * hl.hx;
+    const float y0 = ay * hl.ly, y1 = ay * hl.hy, y2 = by * hl.ly, y3 = by * hl.hy;
+    const float z0 = az * hl.lz, z1 = az * hl.hz, z2 = bz * hl.lz, z3 = bz * hl.hz;
+    const float nx = fminf(fminf(x0, x1), fminf(x2, x3)), fx = fmaxf(fmaxf(x0, x1), fmaxf(x2, x3));
+    const float ny = fminf(fminf(y0, y1), fminf(y2, y3)), fy = fmaxf(fmaxf(y0, y1), fmaxf(y2, y3));
+    const float nz = fminf(fminf(z0, z1), fminf(z2, z3)), fz = fmaxf(fmaxf(z0, z1), fmaxf(z2, z3));
+    const float gx = gl * fmaxf(fabsf(hl.lx), fabsf(hl.hx)), gy = gl * fmaxf(fabsf(hl.ly), fabsf(hl.hy)),
+                gz = gl * fmaxf(fabsf(hl.lz), fabsf(hl.hz));
+    const float tn = fmaxf(fmaxf(nx - gx, ny - gy), nz - gz);
+    const float tf = fminf(fminf(fx + gx, fy + gy), fz + gz);
+    const bool cull = tn > tf || tf < 0.f;
+    return !cull || !(fmaxf(fmaxf(gx, gy), gz) < __builtin_inff());
+}
+
 // Screen of 8 primitives g .. g + 7 of n: words a0, a1 hold (nx, ny) of slots g .. g + 7 as f16,
 // z the nz of slots g .. g + 7 (two per word). Bit j: slot g + j needs the full test.
 // Bit j set iff the f16 dot D_j of slot g + j lies in (blo, ahi]: the det band mapped back through

@@ -214,6 +214,10 @@ struct RenderParams {
     // read it; after the fields above, and read by those kernels only.
     const float2_t* pads;
     int32_t pads_stride;
+    // The primary kernels' wave cull (scan.h flat_leaf_step WCULL): non-zero, a leaf's
+    // clusters are tested against the wave's direction hull before the per-ray tests. Read by
+    // HYBRID's primary kernels only; same output bits either way.
+    int32_t wave_cull;
 };
 
 // The eyes of a launch's cameras, by value, for the kernel that fills the table.

@@ -174,9 +174,11 @@ __global__ __launch_bounds__(256, OCC) void render_kernel(RenderParams P) {
             // the camera's row: the frame index and the stride are wave-uniform, the base stays in SGPRs
             const int32_t row = P.nfcam > 0 ? __builtin_amdgcn_readfirstlane(fidx) : 0;
             const float2_t* pads = uniform_global(P.pads) + int64_t(row) * P.pads_stride;
-            intersect_scene<SCHED, FLAV_PRIMARY_PADS, COUNT>(S, eye, dir, active, id, err, ct, P.hyb_a, P.hyb_b, pads);
+            intersect_scene<SCHED, FLAV_PRIMARY_PADS, COUNT>(S, eye, dir, active, id, err, ct, P.hyb_a, P.hyb_b, pads,
+                                                             P.wave_cull);
         } else {
-            intersect_scene<SCHED, FLAV_PRIMARY, COUNT>(S, eye, dir, active, id, err, ct, P.hyb_a, P.hyb_b);
+            intersect_scene<SCHED, FLAV_PRIMARY, COUNT>(S, eye, dir, active, id, err, ct, P.hyb_a, P.hyb_b, nullptr,
+                                                        P.wave_cull);
         }
         if (active) {
             const DMaterial& mat = S->mats[id.material];
@@ -290,6 +292,16 @@ __global__ __launch_bounds__(256, OCC) void render_kernel(RenderParams P) {
                 for (int off = 32; off > 0; off >>= 1) x2 += __shfl_xor(x2, off);
                 if (lane == 0 && x2) atomicAdd(C + 22 + k, (unsigned long long)x2);
             }
+        }
+        // counters[27..29] (HYBRID's primaries): the wave cull's culled (wave, cluster) pairs and the
+        // lane-private cluster loop's wave iterations, both counted by lane 0; the cluster tests run
+        if constexpr (SCHED == SCHED_HYBRID && PRIMARY) {
+            if (lane == 0 && ct.culled) atomicAdd(C + 27, (unsigned long long)ct.culled);
+            if (lane == 0 && ct.lp_wave) atomicAdd(C + 28, (unsigned long long)ct.lp_wave);
+            uint32_t x2 = ct.ctest;
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) x2 += __shfl_xor(x2, off);
+            if (lane == 0 && x2) atomicAdd(C + 29, (unsigned long long)x2);
         }
         // counters[10..15]: wave clocks in DFS passes, lane-private scans, dealt rounds, whole
         // wave, per-step preparation, whole FLAT/HYBRID scan (phases: diagnostic build only)

@@ -145,6 +145,60 @@ __device__ __forceinline__ int32_t wave_incl_max(int32_t x) {
     return x;
 }
 
+// The wave's largest x (identity -inf), wave-uniform; NaN lanes do not count (v_max_f32).
+__device__ __forceinline__ float wave_max_f(float x) {
+    constexpr int lo = -8388608;  // the bits of -inf
+#define ATR_DPP_MAXF(ctrl, rows) \
+    x = fmaxf(x, __int_as_float(__builtin_amdgcn_update_dpp(lo, __float_as_int(x), ctrl, rows, 0xf, false)))
+    ATR_DPP_MAXF(0x111, 0xf);
+    ATR_DPP_MAXF(0x112, 0xf);
+    ATR_DPP_MAXF(0x114, 0xf);
+    ATR_DPP_MAXF(0x118, 0xf);
+    ATR_DPP_MAXF(0x142, 0xa);
+    ATR_DPP_MAXF(0x143, 0xc);
+#undef ATR_DPP_MAXF
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 63));
+}
+
+// The direction hull (cluster.h WaveHull) of the lanes `in` of a wave of one-origin rays.
+__device__ __forceinline__ WaveHull wave_hull(const Ray& r, bool in) {
+    constexpr float inf = __builtin_inff();
+    WaveHull hl;
+    const bool fin = fabsf(r.inv.x) < inf && fabsf(r.inv.y) < inf && fabsf(r.inv.z) < inf;
+    hl.lx = -wave_max_f(in ? -r.inv.x : -inf);
+    hl.hx = wave_max_f(in ? r.inv.x : -inf);
+    hl.ly = -wave_max_f(in ? -r.inv.y : -inf);
+    hl.hy = wave_max_f(in ? r.inv.y : -inf);
+    hl.lz = -wave_max_f(in ? -r.inv.z : -inf);
+    hl.hz = wave_max_f(in ? r.inv.z : -inf);
+    hl.ok = __ballot(in) != 0 && __ballot(in && !fin) == 0 && (hl.lx > 0.f || hl.hx < 0.f) &&
+            (hl.ly > 0.f || hl.hy < 0.f) && (hl.lz > 0.f || hl.hz < 0.f);
+    return hl;
+}
+
+// A hull in one VGPR: lane k < 6 holds value k; an unusable hull is a NaN in lane 0.
+__device__ __forceinline__ float hull_pack(const WaveHull& hl, int ln) {
+    const float v = ln == 0 ? hl.lx : ln == 1 ? hl.hx : ln == 2 ? hl.ly : ln == 3 ? hl.hy : ln == 4 ? hl.lz : hl.hz;
+    return hl.ok || ln != 0 ? v : __builtin_nanf("");
+}
+__device__ __forceinline__ WaveHull hull_unpack(float hv) {
+    auto at = [&](int k) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(hv), k)); };
+    WaveHull hl;
+    hl.lx = at(0); hl.hx = at(1); hl.ly = at(2); hl.hy = at(3); hl.lz = at(4); hl.hz = at(5);
+    hl.ok = hl.lx == hl.lx;
+    return hl;
+}
+
+// Position of the j-th set bit (j from 0) of x; j < popcount(x).
+__device__ __forceinline__ uint32_t nth_set_bit(uint32_t x, uint32_t j) {
+    uint32_t b = 0, n;
+    n = uint32_t(__popc(x & 0xFFFFu)); if (j >= n) { j -= n; x >>= 16; b += 16; }
+    n = uint32_t(__popc(x & 0xFFu)); if (j >= n) { j -= n; x >>= 8; b += 8; }
+    n = uint32_t(__popc(x & 0xFu)); if (j >= n) { j -= n; x >>= 4; b += 4; }
+    n = uint32_t(__popc(x & 0x3u)); if (j >= n) { j -= n; x >>= 2; b += 2; }
+    return b + (j >= (x & 1u) ? 1u : 0u);
+}
+
 // Phase clocks of the FLAT/HYBRID scans (atr_render_phase_clocks): compiled only into the
 // diagnostic build (make DIAG=1). In the product build the statements vanish; even discarded under
 // `if constexpr` they changed the product kernel's register allocation.
@@ -403,10 +457,21 @@ __device__ __forceinline__ void flat_pass(const Ray& r, const DModel& m, int w, 
 // leaf, or asks for a re-walk. UO: one origin for the whole wave. NUV: u and v feed no output.
 // PADS: the box growths of each cluster come from `pads`, the camera's row of the per-camera table
 // at this model's first cluster (cluster.h cluster_grow; primary flavour only, wave-uniform).
-template <bool COUNT, bool HYB, bool UO, bool NUV, int K = kLeafBuf, bool PADS = false>
+//
+// WCULL (the one-origin primary flavours; hv: the wave's direction hull, hull_pack): before the
+// scan, the clusters of each distinct leaf of the step are tested once per wave against the hull
+// (cluster_hull_keep), lanes as clusters, two leaves at a time in the wave's halves; a ballot is the
+// leaf's survivor mask `sv`, kept by every lane that holds the leaf. The scan then visits the
+// survivors alone: a culled cluster returns 0 from cluster_cands in every lane, so each lane's
+// sequence of bounds, and with it every output and counter of a lane-private step, is what it was
+// (DESIGN.md §4b). Leaves of more than 32 clusters keep them all (sv all ones: survivor j is
+// cluster j).
+template <bool COUNT, bool HYB, bool UO, bool NUV, int K = kLeafBuf, bool PADS = false, bool WCULL = false>
 __device__ __forceinline__ void flat_leaf_step(const Ray& r, const DModel& m, int w, int ln, bool live, FlatQ& q,
-                                               Ctr& ct, int32_t hyb_a, int32_t hyb_b, const float2_t* pads = nullptr) {
+                                               Ctr& ct, int32_t hyb_a, int32_t hyb_b, const float2_t* pads = nullptr,
+                                               float hv = 0.f) {
     static_assert(!PADS || UO, "the table holds one origin per camera");
+    static_assert(!WCULL || (UO && K >= 2), "the hull is of one origin's directions; sv's LDS slot");
     FlatLds<K, !NUV>& L = flat_lds<K, !NUV>();
     // flavour of the scan (primary-only, camera, bounce rays) -> early screen normals (cluster.h)
     constexpr bool kEarly = ((PADS ? 8 : NUV ? 1 : UO ? 2 : 4) & ATR_EARLY_NRM) != 0;
@@ -417,6 +482,47 @@ __device__ __forceinline__ void flat_leaf_step(const Ray& r, const DModel& m, in
         cf = cr.x;
         cn = cr.y;
         if constexpr (COUNT) { ct.leaf += 1; ct.cbox += cn; }
+    }
+    [[maybe_unused]] uint32_t sv = 0xFFFFFFFFu;  // WCULL: the surviving clusters of the lane's leaf
+    if constexpr (WCULL) {
+        const WaveHull hl = hull_unpack(hv);
+        if (hl.ok) {
+            const bool small = live && cn > 0 && cn <= 32u;
+            unsigned long long todo = __ballot(small);
+            while (todo) {  // wave-uniform: two distinct leaves per iteration
+                const int la = __builtin_ctzll(todo);
+                const uint32_t cfa = uint32_t(__builtin_amdgcn_readlane(int(cf), la));
+                const uint32_t cna = uint32_t(__builtin_amdgcn_readlane(int(cn), la));
+                const bool in_a = small && cf == cfa;  // leaves with clusters have distinct firsts
+                todo &= ~__ballot(in_a);
+                const bool two = todo != 0;
+                const int lb = two ? __builtin_ctzll(todo) : la;
+                const uint32_t cfb = uint32_t(__builtin_amdgcn_readlane(int(cf), lb));
+                const uint32_t cnb = two ? uint32_t(__builtin_amdgcn_readlane(int(cn), lb)) : 0u;
+                const bool in_b = two && small && cf == cfb;
+                todo &= ~__ballot(in_b);
+                const uint32_t i = uint32_t(ln) & 31u;
+                const bool hi_half = ln >= 32;
+                bool keep = false;
+                if (i < (hi_half ? cnb : cna)) {
+                    const uint32_t c = (hi_half ? cfb : cfa) + i;
+                    const float4_t lo = m.clus[kClusterBlock * size_t(c)], hi = m.clus[kClusterBlock * size_t(c) + 1];
+                    float gl;
+                    if constexpr (PADS) gl = pads[c].x;
+                    else gl = cluster_grow(r.o, lo, hi).x;
+                    keep = cluster_hull_keep(r.o, hl, lo, hi, gl);
+                }
+                const unsigned long long kept = __ballot(keep);
+                if (in_a) sv = uint32_t(kept);
+                if (in_b) sv = uint32_t(kept >> 32);
+                if constexpr (COUNT)
+                    ct.culled += ln == 0 ? cna + cnb - uint32_t(__popcll(kept)) : 0u;
+            }
+            if (small) cn = uint32_t(__popc(sv));  // the counts below are of the survivors
+        }
+        // the mask waits in the lane's first leaf-distance slot, dead between two passes (K >= 2:
+        // flat_pass reads back entry K - 1 alone), not in a register held through the scan
+        L.lbd[w][0][ln] = __uint_as_float(sv);
     }
     const uint32_t incl = wave_incl_add(cn);  // inclusive prefix sum over the lanes
     const uint32_t excl = incl - cn;
@@ -434,14 +540,22 @@ __device__ __forceinline__ void flat_leaf_step(const Ray& r, const DModel& m, in
                   // of each iteration are compacted over the wave
         const uint32_t mxc = uint32_t(__builtin_amdgcn_readlane(wave_incl_max(int32_t(cn)), 63));
         for (uint32_t i = 0; i < mxc; ++i) {
-            uint32_t cm = 0;
+            uint32_t cm = 0, ci = i;
+            if constexpr (COUNT && WCULL) ct.lp_wave += ln == 0 ? 1u : 0u;
+            if constexpr (WCULL) {  // the survivors not yet visited, ascending
+                const uint32_t left = __float_as_uint(L.lbd[w][0][ln]);
+                if (left) ci = uint32_t(__builtin_ctz(left));
+                L.lbd[w][0][ln] = __uint_as_float(left & (left - 1u));
+                __asm__ volatile("" ::: "memory");  // re-read every iteration, not carried in a register
+            }
             if (i < cn) {
-                const uint32_t c = cf + i;
+                const uint32_t c = cf + ci;
+                if constexpr (COUNT && WCULL) ct.ctest += 1;
                 const float bound = __uint_as_float(uint32_t(L.key[w][ln] >> 32));
                 cm = cluster_cands<COUNT, kEarly, PADS>(r, m, c, m.clus[kClusterBlock * size_t(c)],
                                                 m.clus[kClusterBlock * size_t(c) + 1], bound, ct, pads);
             }
-            cand_rounds<COUNT, UO, NUV, true, K>(r, m, w, ln, cm, kMaxClusterSize * (cf + i), ln, ct);
+            cand_rounds<COUNT, UO, NUV, true, K>(r, m, w, ln, cm, kMaxClusterSize * (cf + ci), ln, ct);
         }
     }
     ATR_PCLK(if (!deal) ct.t_lp += uint32_t(clock64() - tc1));
@@ -465,9 +579,15 @@ __device__ __forceinline__ void flat_leaf_step(const Ray& r, const DModel& m, in
         qr.s0 = qr.inv.x < 0;
         qr.s1 = qr.inv.y < 0;
         qr.s2 = qr.inv.z < 0;
-        const uint32_t c = uint32_t(__shfl(int(cf), src)) + (k - uint32_t(__shfl(int(excl), src)));
+        uint32_t ci = k - uint32_t(__shfl(int(excl), src));  // the item's place among its owner's
+        if constexpr (WCULL) {  // survivors -> its cluster within the leaf
+            const uint32_t os = __float_as_uint(L.lbd[w][0][src]);
+            if (ci < uint32_t(__popc(os))) ci = nth_set_bit(os, ci);
+        }
+        const uint32_t c = uint32_t(__shfl(int(cf), src)) + ci;
         uint32_t cm = 0;
         if (valid) {
+            if constexpr (COUNT && WCULL) ct.ctest += 1;
             const float bound = __uint_as_float(uint32_t(L.key[w][own] >> 32));
             cm = cluster_cands<COUNT, kEarly, PADS>(qr, m, c, m.clus[kClusterBlock * size_t(c)],
                                                     m.clus[kClusterBlock * size_t(c) + 1], bound, ct, pads);
@@ -507,19 +627,26 @@ __device__ __forceinline__ void flat_result(const DModel& m, bool active, int w,
 // One tree query of every active lane of the wave (called by all 64 lanes, converged): passes and
 // leaf steps until every lane's query is done. Flags as above.
 template <bool COUNT, bool HYB = false, bool LDSB = false, bool UO = false, bool UT = false, bool NUV = false,
-          bool NEAR = false, int K = kLeafBuf, bool PADS = false>
+          bool NEAR = false, int K = kLeafBuf, bool PADS = false, bool WCULL = false>
 __device__ __forceinline__ void tree_closest_flat(const Ray& r, const DModel& m, bool active, Hit& h, int& err,
                                                   Ctr& ct, int32_t hyb_a = 0, int32_t hyb_b = 0,
-                                                  const float2_t* pads = nullptr) {
+                                                  const float2_t* pads = nullptr, int32_t wcull = 0) {
     const int w = threadIdx.x >> 6, ln = threadIdx.x & 63;
     ATR_PCLK(uint64_t tcs = clock64());
     FlatQ q = flat_begin<COUNT, K, !NUV>(r, m, active, w, ln, ct);
+    // WCULL: the direction hull of the lanes that passed the root box, once per query; switched off
+    // (wcull == 0, wave-uniform) the hull is unusable and every leaf step keeps all its clusters
+    // (the hull waits in one VGPR, hull_pack, instead of seven SGPRs held through the passes)
+    [[maybe_unused]] float hv = __builtin_nanf("");
+    if constexpr (WCULL) {
+        if (wcull) hv = hull_pack(wave_hull(r, !q.done), ln);
+    }
     for (;;) {
         ATR_PCLK(const uint64_t tc0 = clock64());
         flat_pass<COUNT, LDSB, UT, NEAR, K, !NUV>(r, m, w, ln, q, err, ct);
         ATR_PCLK(ct.t_pass += uint32_t(clock64() - tc0));
         if (__ballot(!q.done) == 0) break;
-        flat_leaf_step<COUNT, HYB, UO, NUV, K, PADS>(r, m, w, ln, !q.done, q, ct, hyb_a, hyb_b, pads);
+        flat_leaf_step<COUNT, HYB, UO, NUV, K, PADS, WCULL>(r, m, w, ln, !q.done, q, ct, hyb_a, hyb_b, pads, hv);
     }
     flat_result<NUV, K>(m, active, w, ln, h);
     ATR_PCLK(ct.t_scan += uint32_t(clock64() - tcs));
@@ -572,7 +699,7 @@ struct SceneHit {
 template <int SCHED, int FLAV, bool COUNT, int KB = kLeafBuf>
 __device__ __forceinline__ SceneHit intersect_models(const DScene* __restrict__ S, V3 o, V3 d, bool active, int& err,
                                                     Ctr& ct, int32_t hyb_a, int32_t hyb_b,
-                                                    const float2_t* pads = nullptr) {
+                                                    const float2_t* pads = nullptr, int32_t wcull = 0) {
     const Ray r = make_ray(o, d);  // renderer.cpp:41-44
     SceneHit sh{kMaxFloat, 0.f, 0.f, 0u, -1};
     const int32_t nmodels = __builtin_amdgcn_readfirstlane(S->nmodels);  // uniform: an SGPR, not a VGPR
@@ -586,10 +713,11 @@ __device__ __forceinline__ SceneHit intersect_models(const DScene* __restrict__ 
             } else if constexpr (FLAV == FLAV_CAMERA)
                 tree_closest_flat<COUNT, true, true, true, true, false>(r, m, active, h, err, ct, hyb_a, hyb_b);
             else if constexpr (FLAV == FLAV_PRIMARY)
-                tree_closest_flat<COUNT, true, true, true, true, true>(r, m, active, h, err, ct, hyb_a, hyb_b);
+                tree_closest_flat<COUNT, true, true, true, true, true, false, kLeafBuf, false, true>(
+                    r, m, active, h, err, ct, hyb_a, hyb_b, nullptr, wcull);
             else if constexpr (FLAV == FLAV_PRIMARY_PADS)
-                tree_closest_flat<COUNT, true, true, true, true, true, false, kLeafBuf, true>(
-                    r, m, active, h, err, ct, hyb_a, hyb_b, pads + __builtin_amdgcn_readfirstlane(m.cl_base));
+                tree_closest_flat<COUNT, true, true, true, true, true, false, kLeafBuf, true, true>(
+                    r, m, active, h, err, ct, hyb_a, hyb_b, pads + __builtin_amdgcn_readfirstlane(m.cl_base), wcull);
             else if constexpr (FLAV == FLAV_HYB_BOUNCE)
                 tree_closest_flat<COUNT, true, false, false, false, false>(r, m, active, h, err, ct, hyb_a, hyb_b);
             else  // bounce rays: near-first passes into the LDS leaf buffer, every step dealt
@@ -616,8 +744,8 @@ __device__ __forceinline__ SceneHit intersect_models(const DScene* __restrict__ 
 template <int SCHED, int FLAV, bool COUNT>
 __device__ __forceinline__ void intersect_scene(const DScene* __restrict__ S, V3 o, V3 d, bool active, Isect& id,
                                                 int& err, Ctr& ct, int32_t hyb_a, int32_t hyb_b,
-                                                const float2_t* pads = nullptr) {
-    const SceneHit sh = intersect_models<SCHED, FLAV, COUNT>(S, o, d, active, err, ct, hyb_a, hyb_b, pads);
+                                                const float2_t* pads = nullptr, int32_t wcull = 0) {
+    const SceneHit sh = intersect_models<SCHED, FLAV, COUNT>(S, o, d, active, err, ct, hyb_a, hyb_b, pads, wcull);
     if (!active) return;
     scene_finish(S, o, d, sh.best, sh.face, sh.fu, sh.fv, sh.nm, id);  // :86-160
 }

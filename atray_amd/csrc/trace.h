@@ -30,6 +30,10 @@ struct Ctr {
     // SIMD efficiency (atr_render_simd_counters): wave-level iterations of the full-test candidate
     // loops, DFS loop iterations at wave and lane level, dealt rounds and the items they carried
     uint32_t cand_wave = 0, node_wave = 0, node_lane = 0, round_wave = 0, round_items = 0;
+    // the wave cull (atr_render_cull_counters): (wave, cluster) pairs culled against the direction
+    // hull (counted by lane 0), wave-level iterations of the lane-private cluster loop, cluster
+    // tests run (lane level)
+    uint32_t culled = 0, lp_wave = 0, ctest = 0;
 };
 
 // 1 in the lowest active lane of the wavefront (counts a divergent loop's wave-level iterations)

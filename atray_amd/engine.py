@@ -116,7 +116,7 @@ EXPORTS = [
     "atr_pack_bgr_masked_bound", "atr_pack_bgr_masked", "atr_scatter_bgr_masked", "atr_unpack_masked",
     "atr_unpack_masked_ranks",
     "atr_render_plan_info", "atr_workspace_info", "atr_render_start_samples",
-    "atr_render_start_adaptive", "atr_render_adaptive_info",
+    "atr_render_start_adaptive", "atr_render_adaptive_info", "atr_render_cull_counters",
 ]
 # the diagnostic build's extra symbols (include/atray_diag.h; make -C atray_amd/csrc DIAG=1)
 DIAG_EXPORTS = ["atr_render_wave_trace", "atr_render_phase_clocks", "atr_render_path_counters",
@@ -172,6 +172,7 @@ def lib():
         "atr_render_adaptive_info": ([vp, i64 * 4], C.c_int),
         "atr_render_packed_size": ([vp, i32], i64),
         "atr_render_counters": ([vp, P(atr_camera), vp, i32, C.c_uint64, i32, i64 * 10], C.c_int),
+        "atr_render_cull_counters": ([vp, P(atr_camera), vp, i32, C.c_uint64, i32, i64 * 5], C.c_int),
         "atr_render_tile_costs": ([vp, P(atr_camera), vp, i32, C.c_uint64, vp], C.c_int),
         "atr_render_wave_trace": ([vp, P(atr_camera), vp, i32, C.c_uint64, i32, vp, i64, P(i64)], C.c_int),
         "atr_packed_pixel_map": ([vp, i32, i32, i32, vp, i64], i64),
@@ -538,6 +539,14 @@ class Engine:
         keys = ["n_rays", "n_box", "n_tri", "n_leaf", "wave_tri_iters", "passes", "box_all", "waves",
                 "cluster_boxes", "screened"]
         return dict(zip(keys, [int(x) for x in out]))
+
+    def cull_counters(self, cam, tiles, seed, variant=ATR_KERNEL_AUTO):
+        """The primary kernels' wave cull in one instrumented render (atr_render_cull_counters)."""
+        arr, n = tiles if isinstance(tiles, tuple) else tiles_array(tiles)
+        out = (C.c_int64 * 5)()
+        check(lib().atr_render_cull_counters(self.h, C.byref(cam), C.cast(arr, C.c_void_p), n,
+                                             C.c_uint64(seed & (2**64 - 1)), int(variant), out), "cull counters")
+        return dict(zip(["culled", "lane_private_iters", "dealt_rounds", "dealt_items", "cluster_tests"], [int(x) for x in out]))
 
     def tile_costs(self, cam, tiles, seed):
         """Shader clocks spent per tile by one render of `tiles` (load-balance calibration)."""

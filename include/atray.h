@@ -151,7 +151,9 @@ int atr_write_bmp(const uint32_t* pixels, int32_t width, int32_t height, const c
 typedef struct atr_ctx atr_ctx;
 /* atr_create reads one environment variable, for A/B runs: ATR_CAMERA_PADS=0 makes this context's
    primary-only kernels compute each cluster's box growths per ray instead of reading them from the
-   per-camera table; unset or any other value: the table. Same output bits either way. */
+   per-camera table; unset or any other value: the table. Same output bits either way.
+   And a second one: ATR_WAVE_CULL=0 makes them test every cluster of a leaf per ray instead of
+   first culling the leaf's clusters against the wave's direction hull; same bits. */
 int atr_create(int device, atr_ctx** out);
 int atr_destroy(atr_ctx* ctx);
 const char* atr_version(void);
@@ -359,6 +361,13 @@ int atr_render_tile_costs(atr_ctx* ctx, const atr_camera* cam, const atr_tile* t
    boxes tested and [9] primitives screened by the clustered scan. */
 int atr_render_counters(atr_ctx* ctx, const atr_camera* cam, const atr_tile* tiles, int32_t ntiles,
                         uint64_t seed, int32_t variant, int64_t counters_out[10]);
+/* Diagnostic, synchronous: the same instrumented render's counters of the primary kernels' wave
+   cull: [0] (wavefront, cluster) pairs culled against the wave's direction hull
+   before the per-ray tests (0 with ATR_WAVE_CULL=0 and for every kernel without the cull),
+   [1] wave-level iterations of the lane-private cluster loop, [2] dealt rounds, [3] dealt items,
+   [4] the per-ray cluster tests run ([8] of atr_render_counters less the culled ones). */
+int atr_render_cull_counters(atr_ctx* ctx, const atr_camera* cam, const atr_tile* tiles, int32_t ntiles,
+                             uint64_t seed, int32_t variant, int64_t counters_out[5]);
 /* Number of pixels a PACKED render of these tiles writes. */
 int64_t atr_render_packed_size(const atr_tile* tiles, int32_t ntiles);
 /* Host-only: pixel index (y * width + x) of every slot of a PACKED render of these tiles, in
