@@ -40,6 +40,8 @@ extern "C" hipError_t atr_launch_path_sort(const atr::PathParams& P, int ncu, hi
 extern "C" hipError_t atr_launch_path_live(const atr::PathParams& P, hipStream_t s);
 extern "C" hipError_t atr_launch_path_camera_adaptive(const atr::PathParams& P, int ncu, hipStream_t s);
 extern "C" hipError_t atr_launch_path_resolve_adaptive(const atr::PathParams& P, hipStream_t s);
+extern "C" hipError_t atr_launch_query_sort(const atr::QueryParams& P, int ncu, hipStream_t s);
+extern "C" hipError_t atr_launch_query(const atr::QueryParams& P, int lane, int ncu, hipStream_t s);
 extern "C" hipError_t atr_launch_tile_casts(const atr_tile* tiles, int32_t ntiles, int32_t width,
                                             const uint32_t* casts, int64_t* out, hipStream_t s);
 extern "C" hipError_t atr_launch_packed_tile_casts(const int32_t* slot_tile, int64_t nslots, const uint32_t* casts,
@@ -323,6 +325,18 @@ struct atr_ctx {
     bool camera_pads = true;
     // ATR_WAVE_CULL at atr_create (0 = the primary kernels test every cluster of a leaf per ray)
     bool wave_cull = true;
+    // Ray queries' workspace (atr_trace_rays, query.hip), apart from the path workspaces and grow-only:
+    // `rays` = {key, rank} and the key order for `cap` rays (12 B each; sorted batches only) and, in
+    // its first 256 B, the head counter; `bins` = `nbins` arrival counters (zero between calls: the
+    // bin scan leaves them so), their starts and block sums. One per context: a call on another
+    // stream than the last first waits (on the GPU) for `ev`, recorded after every call.
+    struct QueryWS {
+        DevBuf rays, bins;
+        int64_t cap = 0, nbins = 0;
+        hipEvent_t ev = nullptr;
+        hipStream_t stream = nullptr;
+        bool used = false;
+    } query_ws;
 };
 
 namespace {
@@ -1310,6 +1324,9 @@ int atr_destroy(atr_ctx* c) {
         if (e) (void)hipEventDestroy(e);
     if (c->tring) (void)hipFree(c->tring);
     if (c->adapt_info) (void)hipFree(c->adapt_info);
+    if (c->query_ws.rays.p) (void)hipFree(c->query_ws.rays.p);
+    if (c->query_ws.bins.p) (void)hipFree(c->query_ws.bins.p);
+    if (c->query_ws.ev) (void)hipEventDestroy(c->query_ws.ev);
     for (atr_ctx::PadSlot& q : c->pad_slot) {
         if (q.mem.p) (void)hipFree(q.mem.p);
         if (q.built) (void)hipEventDestroy(q.built);
@@ -1694,6 +1711,106 @@ int atr_render_start_adaptive(atr_ctx* c, const atr_camera* cam, const atr_tile*
     c->have_render = true;
     c->last_stream = s;
     c->last_ntiles = ntiles;
+    return ATR_OK;
+}
+
+// A batch of the caller's rays (atray.h): with an order, the batch's keys, the bin
+// scan and the key order (query.hip, paths.hip); then the persistent query launch. The traced rays
+// go through a set of the ring, as a render's do (launch_render).
+int atr_trace_rays(atr_ctx* c, const float* origins, const float* directions, int64_t nrays, const atr_ray_hits* hits,
+                   int32_t variant, int32_t sort_bits, void* stream) {
+    if (!c) return ATR_E_INVALID;
+    if (nrays < 0 || nrays >= (int64_t(1) << 31)) return ATR_E_INVALID;
+    if (nrays > 0 && (!hits || !origins || !directions)) return ATR_E_INVALID;
+    if (variant != ATR_KERNEL_AUTO && variant != ATR_KERNEL_FLAT && variant != ATR_KERNEL_LANE) return ATR_E_INVALID;
+    if (sort_bits != -1 && sort_bits != 0 && (sort_bits < 2 || sort_bits > kMaxSortBits)) return ATR_E_INVALID;
+    if (!c->d_scene) return ATR_E_NOSCENE;
+    if (nrays == 0) return ATR_OK;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int32_t bits = sort_bits < 0 ? c->tune.path_sort_bits : sort_bits;
+    while (bits > 0 && (int64_t(kSortDirs) * kSortDirs << (3 * bits)) > kSortBinsMax) --bits;
+    const int64_t nbins = bits > 0 ? int64_t(kSortDirs) * kSortDirs << (3 * bits) : 0;
+    atr_ctx::QueryWS& ws = c->query_ws;
+    if (!ws.ev) HIPCHK(hipEventCreateWithFlags(&ws.ev, hipEventDisableTiming));
+    const int64_t need = bits > 0 ? nrays : 0;
+    if (!ws.rays.p || ws.cap < need || ws.nbins < nbins) {  // grow: after the last call that used it
+        if (ws.used) HIPCHK(hipEventSynchronize(ws.ev));
+        int rc;
+        if (!ws.rays.p || ws.cap < need) {
+            if ((rc = ensure_buf(ws.rays, 256 + size_t(std::max(need, ws.cap)) * 12, false))) return rc;
+            ws.cap = std::max(need, ws.cap);
+        }
+        if (ws.nbins < nbins) {
+            const size_t bytes = size_t(nbins) * 8 + size_t(nbins / kSortChunk) * 4;
+            ws.nbins = 0;
+            if ((rc = ensure_buf(ws.bins, bytes, false))) return rc;
+            HIPCHK(hipMemset(ws.bins.p, 0, bytes));
+            ws.nbins = nbins;
+        }
+    }
+    if (ws.used && ws.stream != s) HIPCHK(hipStreamWaitEvent(s, ws.ev, 0));
+    QueryParams Q;
+    std::memset(&Q, 0, sizeof(Q));
+    Q.scene = c->d_scene;
+    Q.o = origins;
+    Q.d = directions;
+    Q.n = uint32_t(nrays);
+    Q.hyb_a = c->tune.hybrid_a;
+    Q.hyb_b = c->tune.hybrid_b;
+    Q.t = hits->t;
+    Q.face = hits->face;
+    Q.model = hits->model;
+    Q.uv = hits->uv;
+    Q.kind = hits->kind;
+    Q.material = hits->material;
+    Q.normal = hits->normal;
+    Q.error_flag = c->d_error;
+    Q.head = static_cast<uint32_t*>(ws.rays.p);
+    if (bits > 0) {
+        PathSort& so = Q.sort;
+        so.bits = bits;
+        so.nbins = int32_t(nbins);
+        const float* box = c->scene_box;  // the path engine's cells (launch_paths_range)
+        for (int a = 0; a < 3; ++a) {
+            so.lo[a] = box[a];
+            const float ext = box[3 + a] - box[a];
+            so.sc[a] = ext > 0.0f ? float(1 << bits) / ext : 0.0f;
+        }
+        char* rb = static_cast<char*>(ws.rays.p) + 256;
+        so.kr = reinterpret_cast<uint2_t*>(rb);
+        so.perm = reinterpret_cast<uint32_t*>(rb + size_t(ws.cap) * 8);
+        so.hist = static_cast<uint32_t*>(ws.bins.p);
+        so.start = so.hist + ws.nbins;
+        so.part = so.start + ws.nbins;
+    }
+    c->prog_active = false;
+    HIPCHK(hipEventRecord(c->ev_start, s));
+    ws.used = true;  // from here on kernels of this call may be in flight on s
+    ws.stream = s;
+    hipEvent_t done = nullptr;
+    int k = -1;
+    if (hits->traced_rays) {  // a zeroed set of 64 spread counters from the ring (launch_render)
+        k = c->tnext;
+        c->tnext = (k + 1) % kQueueSlots;
+        if (c->tused[k]) HIPCHK(hipStreamWaitEvent(s, c->tev[k], 0));
+        Q.traced_rays = reinterpret_cast<unsigned long long*>(static_cast<char*>(c->tring) + size_t(k) * kTraceBytes);
+    }
+    HIPCHK(hipMemsetAsync(Q.head, 0, sizeof(uint32_t), s));
+    if (bits > 0) HIPCHK(atr_launch_query_sort(Q, c->ncu, s));
+    HIPCHK(atr_launch_query(Q, variant == ATR_KERNEL_LANE ? 1 : 0, c->ncu, s));
+    if (k >= 0) {
+        HIPCHK(atr_launch_traced_finish(Q.traced_rays, hits->traced_rays, s));
+        HIPCHK(hipEventRecord(c->tev[k], s));
+        c->tused[k] = true;
+        done = c->tev[k];
+    }
+    HIPCHK(hipEventRecord(ws.ev, s));
+    HIPCHK(record_stop(c, s, done));
+    HIPCHK(note_launch(c, s, c->ev_last != c->ev_stop));  // a ring event covers it
+    c->have_render = true;
+    c->last_stream = s;
+    c->last_ntiles = 0;
     return ATR_OK;
 }
 

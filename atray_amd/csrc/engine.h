@@ -332,4 +332,37 @@ struct PathParams {
     PathLive live;          // an adaptive pass: read by the path_live_* and *_adaptive kernels only
 };
 
+// A ray query (atr_trace_rays, query.hip): n caller rays, 3 floats each, traced by
+// persistent waves that claim 64 positions at a time on `head`; with sort.bits > 0 position i of
+// the batch is ray sort.perm[i] (the batch in PathSort key order), else ray i. Every output is
+// written at the ray's input index; a null output is not written.
+struct QueryParams {
+    const DScene* scene;
+    const float* o;
+    const float* d;
+    uint32_t n;
+    int32_t hyb_a, hyb_b;
+    float* t;
+    uint32_t* face;
+    int32_t* model;
+    float* uv;
+    int32_t* kind;
+    int32_t* material;
+    float* normal;
+    unsigned long long* traced_rays;  // 64 spread counters (a ring slot), or null
+    int32_t* error_flag;
+    uint32_t* head;  // zeroed before the launch
+    PathSort sort;
+};
+
+// The validity test of a caller's ray (atray.h atr_trace_rays): six finite inputs and a direction
+// normalised to within 2^-20 in len2 (what unit() leaves is within 6 x 2^-24). The comparisons are
+// false for a NaN, and an infinite component fails the first one.
+constexpr float kRayLen2Tol = 9.5367431640625e-07f;  // 0x1p-20f
+ATR_HD bool ray_ok(V3 o, V3 d) {
+    const bool fin = fabsf(o.x) <= kMaxFloat && fabsf(o.y) <= kMaxFloat && fabsf(o.z) <= kMaxFloat &&
+                     fabsf(d.x) <= kMaxFloat && fabsf(d.y) <= kMaxFloat && fabsf(d.z) <= kMaxFloat;
+    return fin && fabsf(len2(d) - 1.0f) <= kRayLen2Tol;
+}
+
 }  // namespace atr

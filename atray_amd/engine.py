@@ -34,6 +34,8 @@ VARIANTS = (ATR_KERNEL_LANE, ATR_KERNEL_FLAT, ATR_KERNEL_HYBRID, ATR_KERNEL_PATH
 MISS = 0xFFFFFFFF
 ATR_SAMPLES_CONVERGED = 0x80000000  # sample_count bit 31: the pixel has stopped (atr_render_start_adaptive)
 MAX_FLOAT = np.float32(3.402823466e38)
+# atr_trace_rays: what a ray met (atr_ray_hits.kind)
+ATR_RAY_SKY, ATR_RAY_TRI, ATR_RAY_SPHERE, ATR_RAY_PLANE, ATR_RAY_INVALID = 0, 1, 2, 3, 4
 
 ERRORS = {-1: "ATR_E_INVALID", -2: "ATR_E_IO", -3: "ATR_E_NOMEM", -4: "ATR_E_NOSCENE",
           -5: "ATR_E_TREE_DEPTH", -6: "ATR_E_TREE_LAYOUT"}
@@ -91,6 +93,12 @@ class atr_frame(C.Structure):
                 ("traced_rays", C.c_void_p)]
 
 
+class atr_ray_hits(C.Structure):
+    _fields_ = [("t", C.c_void_p), ("face", C.c_void_p), ("model", C.c_void_p), ("uv", C.c_void_p),
+                ("kind", C.c_void_p), ("material", C.c_void_p), ("normal", C.c_void_p),
+                ("traced_rays", C.c_void_p)]
+
+
 class atr_tuning(C.Structure):
     _fields_ = [("xcd_chunk", C.c_int32), ("frame_rotate", C.c_int32), ("hybrid_a", C.c_int32),
                 ("hybrid_b", C.c_int32), ("path_batch_log2", C.c_int32), ("cluster_size", C.c_int32),
@@ -117,6 +125,7 @@ EXPORTS = [
     "atr_unpack_masked_ranks",
     "atr_render_plan_info", "atr_workspace_info", "atr_render_start_samples",
     "atr_render_start_adaptive", "atr_render_adaptive_info", "atr_render_cull_counters",
+    "atr_trace_rays",
 ]
 # the diagnostic build's extra symbols (include/atray_diag.h; make -C atray_amd/csrc DIAG=1)
 DIAG_EXPORTS = ["atr_render_wave_trace", "atr_render_phase_clocks", "atr_render_path_counters",
@@ -170,6 +179,7 @@ def lib():
         "atr_render_start_adaptive": ([vp, P(atr_camera), vp, i32, P(atr_frame), C.c_uint64, vp, i32, u32, vp, vp,
                                        C.c_float], C.c_int),
         "atr_render_adaptive_info": ([vp, i64 * 4], C.c_int),
+        "atr_trace_rays": ([vp, vp, vp, i64, P(atr_ray_hits), i32, i32, vp], C.c_int),
         "atr_render_packed_size": ([vp, i32], i64),
         "atr_render_counters": ([vp, P(atr_camera), vp, i32, C.c_uint64, i32, i64 * 10], C.c_int),
         "atr_render_cull_counters": ([vp, P(atr_camera), vp, i32, C.c_uint64, i32, i64 * 5], C.c_int),
@@ -495,6 +505,48 @@ class Engine:
                                               int(first_sample), C.c_void_p(sum_ptr) if sum_ptr else None,
                                               C.c_void_p(count_ptr) if count_ptr else None, float(tolerance)),
               "adaptive pass start")
+
+    # atr_ray_hits outputs: name -> (torch dtype name, elements per ray, fill before the call)
+    _RAY_OUTPUTS = {"t": ("float32", 1), "face": ("int32", 1), "model": ("int32", 1), "uv": ("float32", 2),
+                    "kind": ("int32", 1), "material": ("int32", 1), "normal": ("float32", 3)}
+
+    def trace_rays(self, orig, dirs, variant=ATR_KERNEL_AUTO, sort_bits=-1, stream=None,
+                   outputs=("t", "face", "model", "uv", "kind", "material", "normal")):
+        """atr_trace_rays: the closest hit of every ray of a batch. orig, dirs: contiguous (n, 3) float32
+        tensors on the engine's device; directions normalised (a ray that is not, or not finite, comes
+        back as ATR_RAY_INVALID with the miss record). Enqueued on `stream` (a raw HIP stream), or
+        torch's current one. Returns ({name: tensor} for the requested outputs, in input order -- face
+        as int32 bits, MISS = -1 -- and the traced-ray count as a one-element int64 tensor); valid
+        once the stream has run, e.g. after wait()."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        for name, a in (("orig", orig), ("dirs", dirs)):
+            if not isinstance(a, torch.Tensor) or a.dtype != torch.float32 or a.dim() != 2 or a.shape[1] != 3:
+                raise ValueError(f"{name}: an (n, 3) float32 tensor is required")
+            if a.device != dev:
+                raise ValueError(f"{name}: not on {dev}")
+            if not a.is_contiguous():
+                raise ValueError(f"{name}: not contiguous")
+        if orig.shape[0] != dirs.shape[0]:
+            raise ValueError("orig and dirs differ in length")
+        bad = [k for k in outputs if k not in self._RAY_OUTPUTS]
+        if bad:
+            raise ValueError(f"unknown outputs {bad}")
+        n = int(orig.shape[0])
+        out = {}
+        for k in outputs:
+            dt, per = self._RAY_OUTPUTS[k]
+            out[k] = torch.empty((n, per) if per > 1 else (n,), dtype=getattr(torch, dt), device=dev)
+        traced = torch.zeros(1, dtype=torch.int64, device=dev)
+        hits = atr_ray_hits(*[out[k].data_ptr() if k in out and n else None
+                              for k in ("t", "face", "model", "uv", "kind", "material", "normal")],
+                            traced.data_ptr())
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        check(lib().atr_trace_rays(self.h, C.c_void_p(orig.data_ptr()) if n else None,
+                                   C.c_void_p(dirs.data_ptr()) if n else None, n, C.byref(hits), int(variant),
+                                   int(sort_bits), C.c_void_p(stream) if stream else None), "trace rays")
+        return out, traced
 
     def adaptive_info(self):
         """The last adaptive pass's counts, once wait() returned 0: (pixels live at its start, blocks

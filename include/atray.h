@@ -24,7 +24,9 @@ extern "C" {
 #endif
 
 /* ABI 2 (round 6): atr_tuning gained reserved[4] (zero; room for later knobs without a size
-   change); ABI 1's last two words became path_sort_bits and path_split in round 5. */
+   change); ABI 1's last two words became path_sort_bits and path_split in round 5.
+   atr_trace_rays and atr_ray_hits were added since without a version change: no existing struct
+   or entry point changed. */
 #define ATR_ABI_VERSION 2
 
 enum {
@@ -457,6 +459,47 @@ int atr_render_plan_info(atr_ctx* ctx, const atr_tile* tiles, int32_t ntiles, in
    (cell kernels only): out has ceil(W/8) x ceil(H/8) entries, row major. Synchronous. */
 int atr_render_cell_costs(atr_ctx* ctx, const atr_camera* cam, uint64_t seed, int32_t variant,
                           int64_t* out);
+/* Ray queries: get_intersection_data (renderer.cpp:34-160) for a batch of the caller's own rays
+   (picking, visibility between points, a light sampler or a baker of the caller's, collision
+   probes). origins and directions: DEVICE pointers, 3 floats per ray. Models are visited in upload
+   order with strict <, so the lowest model index wins a tie; then the spheres, then the planes;
+   kind has the reference's precedence: a plane that improved t, else a sphere, else the triangle.
+   Every output is written at the ray's input index.
+   Directions must be normalised: the clustered scan's exclusion proofs assume |d| = 1 up to f32
+   normalisation error. Every ray is tested before it is traced: all six inputs
+   finite and fabsf(len2(d) - 1.0f) <= 0x1p-20f, len2(d) = (d.x*d.x + d.y*d.y) + d.z*d.z in separately
+   rounded f32 operations (v * (1 / sqrtf(len2(v))) in f32 leaves at most 6 x 2^-24). A ray that
+   fails is not traced: it gets kind ATR_RAY_INVALID and the miss record, and does not count in
+   traced_rays. No NaN or zero direction reaches the traversal.
+   variant: ATR_KERNEL_AUTO and ATR_KERNEL_FLAT = the clustered scan in its bounce flavour,
+   ATR_KERNEL_LANE = the per-lane reference scan; the same bits; any other value is ATR_E_INVALID.
+   sort_bits: 0 = the batch is traced in input order; 2..7 = in (direction cell, origin cell) order
+   at that many bits per axis of the scene box (the path engine's queue order, tuning
+   path_sort_bits; 6 at most is used; an origin outside the box counts in the edge cell); -1 = the
+   context's tuning path_sort_bits; any other value is ATR_E_INVALID. No output bit depends on it.
+   The order pays for incoherent batches; pass 0 for a batch that is coherent as it comes (camera
+   rays in pixel order), which the sort pass only slows down.
+   Asynchronous on `stream`, like a render: atr_render_wait covers it (tiles_done 0; a tree-depth
+   flag surfaces as ATR_E_TREE_DEPTH), atr_last_kernel_ms times it. nrays == 0: ATR_OK, nothing is
+   enqueued or written. The context keeps one grow-only query workspace (12 B per ray of the largest
+   sorted batch, 8 B per sort bin), apart from the path workspaces of atr_workspace_info.
+   ATR_E_INVALID: ctx NULL; hits, origins or directions NULL with nrays > 0; nrays < 0 or >= 2^31;
+   a bad variant or sort_bits. ATR_E_NOSCENE before an upload. */
+enum { ATR_RAY_SKY = 0, ATR_RAY_TRI = 1, ATR_RAY_SPHERE = 2, ATR_RAY_PLANE = 3, ATR_RAY_INVALID = 4 };
+typedef struct {           /* DEVICE pointers, one element per ray, input order; any may be NULL */
+    float* t;              /* closest t (> 1e-4, the reference's tolerance); 3.402823466e38 = none */
+    uint32_t* face;        /* face index within its model; 0xFFFFFFFF unless kind == TRI */
+    int32_t* model;        /* model index; -1 unless kind == TRI */
+    float* uv;             /* 2 per ray: barycentrics of the closest MODEL hit found -- left in place
+                              when a sphere or plane is nearer; 0, 0 when no model was hit */
+    int32_t* kind;         /* ATR_RAY_* */
+    int32_t* material;     /* the hit's material index; 0 (sky) for SKY and INVALID */
+    float* normal;         /* 3 per ray: the hit's unit normal (not flipped); 0,0,0 for SKY/INVALID */
+    unsigned long long* traced_rays; /* one accumulator, += rays actually traced */
+} atr_ray_hits;
+int atr_trace_rays(atr_ctx* ctx, const float* origins, const float* directions, int64_t nrays,
+                   const atr_ray_hits* hits, int32_t variant, int32_t sort_bits, void* stream);
+
 /* wait_for_render_from_camera_to_finish: 1 = still running after timeout_ms, 0 = done,
    <0 = error. tiles_done (optional) = tiles of the last render known complete (progress). */
 int atr_render_wait(atr_ctx* ctx, uint32_t timeout_ms, int32_t* tiles_done);
