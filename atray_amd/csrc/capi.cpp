@@ -42,6 +42,7 @@ extern "C" hipError_t atr_launch_path_camera_adaptive(const atr::PathParams& P, 
 extern "C" hipError_t atr_launch_path_resolve_adaptive(const atr::PathParams& P, hipStream_t s);
 extern "C" hipError_t atr_launch_query_sort(const atr::QueryParams& P, int ncu, hipStream_t s);
 extern "C" hipError_t atr_launch_query(const atr::QueryParams& P, int lane, int ncu, hipStream_t s);
+extern "C" hipError_t atr_launch_occlusion(const atr::OcclParams& P, int lane, int ncu, hipStream_t s);
 extern "C" hipError_t atr_launch_tile_casts(const atr_tile* tiles, int32_t ntiles, int32_t width,
                                             const uint32_t* casts, int64_t* out, hipStream_t s);
 extern "C" hipError_t atr_launch_packed_tile_casts(const int32_t* slot_tile, int64_t nslots, const uint32_t* casts,
@@ -1716,16 +1717,26 @@ int atr_render_start_adaptive(atr_ctx* c, const atr_camera* cam, const atr_tile*
 
 // A batch of the caller's rays (atray.h): with an order, the batch's keys, the bin
 // scan and the key order (query.hip, paths.hip); then the persistent query launch. The traced rays
-// go through a set of the ring, as a render's do (launch_render).
-int atr_trace_rays(atr_ctx* c, const float* origins, const float* directions, int64_t nrays, const atr_ray_hits* hits,
-                   int32_t variant, int32_t sort_bits, void* stream) {
+// go through a set of the ring, as a render's do (launch_render). Shared by atr_trace_rays and
+// atr_occluded_rays (occlusion.hip): `launch` gets the batch, its order, the claim
+// counter and the ring's counters in a QueryParams and enqueues the query's own kernel.
+extern "C++" {  // a template
+namespace {
+// The argument checks both queries share (atray.h); `out` is the required output.
+int query_args(atr_ctx* c, const float* origins, const float* directions, int64_t nrays, const void* out,
+               int32_t variant, int32_t sort_bits) {
     if (!c) return ATR_E_INVALID;
     if (nrays < 0 || nrays >= (int64_t(1) << 31)) return ATR_E_INVALID;
-    if (nrays > 0 && (!hits || !origins || !directions)) return ATR_E_INVALID;
+    if (nrays > 0 && (!out || !origins || !directions)) return ATR_E_INVALID;
     if (variant != ATR_KERNEL_AUTO && variant != ATR_KERNEL_FLAT && variant != ATR_KERNEL_LANE) return ATR_E_INVALID;
     if (sort_bits != -1 && sort_bits != 0 && (sort_bits < 2 || sort_bits > kMaxSortBits)) return ATR_E_INVALID;
     if (!c->d_scene) return ATR_E_NOSCENE;
-    if (nrays == 0) return ATR_OK;
+    return ATR_OK;
+}
+
+template <class Launch>
+int query_call(atr_ctx* c, const float* origins, const float* directions, int64_t nrays, int32_t sort_bits,
+               void* stream, unsigned long long* traced_out, Launch launch) {
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     int32_t bits = sort_bits < 0 ? c->tune.path_sort_bits : sort_bits;
@@ -1758,13 +1769,6 @@ int atr_trace_rays(atr_ctx* c, const float* origins, const float* directions, in
     Q.n = uint32_t(nrays);
     Q.hyb_a = c->tune.hybrid_a;
     Q.hyb_b = c->tune.hybrid_b;
-    Q.t = hits->t;
-    Q.face = hits->face;
-    Q.model = hits->model;
-    Q.uv = hits->uv;
-    Q.kind = hits->kind;
-    Q.material = hits->material;
-    Q.normal = hits->normal;
     Q.error_flag = c->d_error;
     Q.head = static_cast<uint32_t*>(ws.rays.p);
     if (bits > 0) {
@@ -1790,7 +1794,7 @@ int atr_trace_rays(atr_ctx* c, const float* origins, const float* directions, in
     ws.stream = s;
     hipEvent_t done = nullptr;
     int k = -1;
-    if (hits->traced_rays) {  // a zeroed set of 64 spread counters from the ring (launch_render)
+    if (traced_out) {  // a zeroed set of 64 spread counters from the ring (launch_render)
         k = c->tnext;
         c->tnext = (k + 1) % kQueueSlots;
         if (c->tused[k]) HIPCHK(hipStreamWaitEvent(s, c->tev[k], 0));
@@ -1798,9 +1802,9 @@ int atr_trace_rays(atr_ctx* c, const float* origins, const float* directions, in
     }
     HIPCHK(hipMemsetAsync(Q.head, 0, sizeof(uint32_t), s));
     if (bits > 0) HIPCHK(atr_launch_query_sort(Q, c->ncu, s));
-    HIPCHK(atr_launch_query(Q, variant == ATR_KERNEL_LANE ? 1 : 0, c->ncu, s));
+    HIPCHK(launch(Q, s));
     if (k >= 0) {
-        HIPCHK(atr_launch_traced_finish(Q.traced_rays, hits->traced_rays, s));
+        HIPCHK(atr_launch_traced_finish(Q.traced_rays, traced_out, s));
         HIPCHK(hipEventRecord(c->tev[k], s));
         c->tused[k] = true;
         done = c->tev[k];
@@ -1812,6 +1816,49 @@ int atr_trace_rays(atr_ctx* c, const float* origins, const float* directions, in
     c->last_stream = s;
     c->last_ntiles = 0;
     return ATR_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int atr_trace_rays(atr_ctx* c, const float* origins, const float* directions, int64_t nrays, const atr_ray_hits* hits,
+                   int32_t variant, int32_t sort_bits, void* stream) {
+    const int rc = query_args(c, origins, directions, nrays, hits, variant, sort_bits);
+    if (rc != ATR_OK || nrays == 0) return rc;
+    return query_call(c, origins, directions, nrays, sort_bits, stream, hits->traced_rays,
+                      [&](QueryParams& Q, hipStream_t s) {
+                          Q.t = hits->t;
+                          Q.face = hits->face;
+                          Q.model = hits->model;
+                          Q.uv = hits->uv;
+                          Q.kind = hits->kind;
+                          Q.material = hits->material;
+                          Q.normal = hits->normal;
+                          return atr_launch_query(Q, variant == ATR_KERNEL_LANE ? 1 : 0, c->ncu, s);
+                      });
+}
+
+// An occlusion query (atray.h): the ray query's order and workspace, its own kernel.
+int atr_occluded_rays(atr_ctx* c, const float* origins, const float* directions, const float* t_max, int64_t nrays,
+                      uint8_t* occluded, unsigned long long* traced_rays, int32_t variant, int32_t sort_bits,
+                      void* stream) {
+    const int rc = query_args(c, origins, directions, nrays, occluded, variant, sort_bits);
+    if (rc != ATR_OK || nrays == 0) return rc;
+    return query_call(c, origins, directions, nrays, sort_bits, stream, traced_rays,
+                      [&](QueryParams& Q, hipStream_t s) {
+                          OcclParams P;
+                          std::memset(&P, 0, sizeof(P));
+                          P.scene = Q.scene;
+                          P.o = Q.o;
+                          P.d = Q.d;
+                          P.tmax = t_max;
+                          P.n = Q.n;
+                          P.out = occluded;
+                          P.traced_rays = Q.traced_rays;
+                          P.error_flag = Q.error_flag;
+                          P.head = Q.head;
+                          P.perm = Q.sort.bits > 0 ? Q.sort.perm : nullptr;
+                          return atr_launch_occlusion(P, variant == ATR_KERNEL_LANE ? 1 : 0, c->ncu, s);
+                      });
 }
 
 int atr_render_adaptive_info(atr_ctx* c, int64_t info_out[4]) {

@@ -355,6 +355,23 @@ struct QueryParams {
     PathSort sort;
 };
 
+// An occlusion query (atr_occluded_rays, occlusion.hip): the batch, its claim counter
+// and its key order as in QueryParams (the order is made by the ray query's own sort kernels, in the
+// same workspace); tmax one float per ray or null (every ray unbounded); out one byte per ray at its
+// input index (ATR_OCCL_*).
+struct OcclParams {
+    const DScene* scene;
+    const float* o;
+    const float* d;
+    const float* tmax;
+    uint32_t n;
+    uint8_t* out;
+    unsigned long long* traced_rays;  // 64 spread counters (a ring slot), or null
+    int32_t* error_flag;
+    uint32_t* head;        // zeroed before the launch
+    const uint32_t* perm;  // sorted launches: position -> ray
+};
+
 // The validity test of a caller's ray (atray.h atr_trace_rays): six finite inputs and a direction
 // normalised to within 2^-20 in len2 (what unit() leaves is within 6 x 2^-24). The comparisons are
 // false for a NaN, and an infinite component fails the first one.

@@ -1,0 +1,205 @@
+// occlusion.hip -- occlusion queries (atr_occluded_rays): for a batch of the caller's
+// rays, is there any hit with kTol < t < t_max -- the reference's own traversal with *td.closest
+// started at the ray's t_max instead of MAX_FLOAT, one byte per ray.
+//   ray_occlusion_kernel  persistent waves claim 64 positions of the batch at a time (the batch's
+//                         key order comes from query.hip's ray_query_keys / ray_query_rank), test
+//                         the spheres and planes, then the models in upload order with the scan's
+//                         bound seeded at t_max (scan.h SEED; LANE: the per-lane reference scan
+//                         started at t_max); a lane retires at its first hit, the model loop ends
+//                         when no lane of the wave is left.
+// A file of its own: the render, path and ray-query kernels' code objects are what they were.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "scan.h"
+
+namespace atr {
+
+__device__ __forceinline__ void load_ray(const float* __restrict__ po, const float* __restrict__ pd, uint32_t e, V3& o,
+                                         V3& d) {
+    const size_t b = 3 * size_t(e);
+    o = mk(po[b], po[b + 1], po[b + 2]);
+    d = mk(pd[b], pd[b + 1], pd[b + 2]);
+}
+
+// The t of shade.h's sphere and plane tests (sphere.h:12-39, plane.h:12-22), the same f32 operations
+// in the same order; 0: no hit.
+__device__ __forceinline__ float sphere_t(V3 o, V3 d, const DSphere& sp) {
+    const V3 pc = sub(o, mk(sp.cx, sp.cy, sp.cz));
+    const float pcs = len2(pc);
+    const float b = 2 * (dot(d, pc));
+    const float bs = b * b;
+    const float c = pcs - sp.r * sp.r;
+    const float dmt = bs - (4 * c);
+    float t = 0;
+    if (!(dmt < 0)) {
+        const float ta = (-b + sqrtf(dmt)) * 0.5f;
+        const float tb = (-b - sqrtf(dmt)) * 0.5f;
+        if (ta <= 0 && tb <= 0) t = 0;
+        else if (tb > 0) t = tb;
+        else t = ta;
+    }
+    return t;
+}
+__device__ __forceinline__ float plane_t(V3 o, V3 d, const DPlane& pl) {
+    const V3 n = mk(pl.nx, pl.ny, pl.nz);
+    const float denom = dot(n, d);
+    float t = 0;
+    if (!(denom > -kTol && denom < kTol)) t = (pl.d - dot(o, n)) / denom;
+    return t;
+}
+
+// Any sphere or plane with kTol < t < T (every lane of the wave; the counts are wave-uniform).
+__device__ __forceinline__ bool occluded_analytic(const DScene* __restrict__ S, V3 o, V3 d, float T) {
+    const int32_t nspheres = __builtin_amdgcn_readfirstlane(S->nspheres), nplanes = __builtin_amdgcn_readfirstlane(S->nplanes);
+    bool occ = false;
+    for (int32_t i = 0; i < nspheres; ++i) {
+        const float t = sphere_t(o, d, uniform_global(S->spheres)[i]);
+        occ = occ || (t > kTol && t < T);
+    }
+    for (int32_t i = 0; i < nplanes; ++i) {
+        const float t = plane_t(o, d, uniform_global(S->planes)[i]);
+        occ = occ || (t > kTol && t < T);
+    }
+    return occ;
+}
+
+// Any triangle of any model with kTol < t < T, for every lane of the wave (converged call; inactive
+// lanes take part in the wave-wide scans). Models in upload order; the lanes a model occludes are
+// inactive for the models after it, and the loop ends once no lane is left. Tree models: the
+// reference's walk (root box, root leaf or the DFS's leaves in ascending distance) with its closest
+// started at T, which ends at the first leaf that improves on it. LANE: the per-lane reference scan;
+// otherwise the clustered scan in the bounce flavour without barycentrics (near-first passes into the
+// LDS leaf buffer, every step dealt, no u/v rows in LDS), the key seeded with T.
+template <bool LANE>
+__device__ __forceinline__ bool occluded_models(const DScene* __restrict__ S, V3 o, V3 d, float T, bool active, int& err,
+                                                Ctr& ct) {
+    const Ray r = make_ray(o, d);
+    bool occ = false;
+    const int32_t nmodels = __builtin_amdgcn_readfirstlane(S->nmodels);
+    for (int32_t i = 0; i < nmodels; ++i) {
+        if (__ballot(active) == 0) break;  // wave-uniform
+        const DModel m = uniform_model(S->models[i]);
+        bool hit = false;
+        if (m.has_tree) {
+            if constexpr (LANE) {
+                if (active) {
+                    Hit h;
+                    tree_closest_lane<false>(r, m, h, err, ct, T);
+                    hit = h.t < T;
+                }
+            } else {
+                constexpr int K = kLeafBuf;
+                const int w = threadIdx.x >> 6, ln = threadIdx.x & 63;
+                const unsigned long long start = static_cast<unsigned long long>(__float_as_uint(T)) << 32;
+                FlatQ q = flat_begin<false, K, false, true>(r, m, active, w, ln, ct, start);
+                for (;;) {
+                    flat_pass<false, true, false, true, K, false>(r, m, w, ln, q, err, ct);
+                    if (__ballot(!q.done) == 0) break;
+                    flat_leaf_step<false, false, false, true, K, false, false, true>(r, m, w, ln, !q.done, q, ct, 0, 0,
+                                                                                     nullptr, 0.f, start);
+                }
+                hit = active && flat_lds<K, false>().key[w][ln] != start;
+            }
+        } else if (active) {  // brute force: the surrounding box, then the faces up to the first hit
+            if (box_entry(r, m.aabb[0], m.aabb[1], m.aabb[2], m.aabb[3], m.aabb[4], m.aabb[5]) != 0) {
+                for (uint32_t j = 0; j < m.nfaces && !hit; ++j) {
+                    const DTri* t = m.tris + j;
+                    float u = 0.f, v = 0.f;
+                    const float tt = tri_hit(r, mk(t->ax, t->ay, t->az), mk(t->abx, t->aby, t->abz),
+                                             mk(t->acx, t->acy, t->acz), u, v);
+                    hit = tt > kTol && tt < T;
+                }
+            }
+        }
+        if (hit) {
+            occ = true;
+            active = false;
+        }
+    }
+    return occ;
+}
+
+// Waves/SIMD: the ray query's 7 (query.hip kQueryOcc). Without the u/v rows the LDS is 20 KB per
+// workgroup, so 8 would fit a CU; built for 8 (64 VGPRs, 31 spilled dwords instead of 6) the query
+// measured 3-14 % slower on the clustered scan and 7-45 % on LANE (one box).
+#ifndef ATR_OCCL_OCC  // experiment builds
+#define ATR_OCCL_OCC 7
+#endif
+constexpr int kOcclOcc = ATR_OCCL_OCC;
+
+template <bool LANE, bool SORT>
+__global__ __launch_bounds__(256, kOcclOcc) void ray_occlusion_kernel(OcclParams P) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t n = uint32_t(__builtin_amdgcn_readfirstlane(int(P.n)));
+    const DScene* S = uniform_global(P.scene);
+    int err = 0;
+    Ctr ct;
+    uint32_t traced = 0;
+    for (;;) {  // every wave leaves once the batch is claimed: the exit every wave reaches
+        uint32_t base = 0;
+        if (lane == 0) base = atomicAdd(P.head, 64u);
+        base = uint32_t(__builtin_amdgcn_readfirstlane(int(__shfl(int(base), 0))));
+        if (base >= n) break;
+        const uint32_t i = base + uint32_t(lane);
+        bool in = i < n;
+        uint32_t e = i;
+        if (SORT && in) {
+            e = P.perm[i];
+            // an index outside the batch, impossible for a complete order, is neither read nor written
+            if (e >= n) {
+                in = false;
+                if (P.error_flag) atomicOr(P.error_flag, 2);
+            }
+        }
+        V3 o = mk(0.f, 0.f, 0.f), d = mk(0.f, 0.f, 1.f);
+        float T = kMaxFloat;
+        bool ok = false;
+        if (in) {
+            V3 ro, rd;
+            load_ray(P.o, P.d, e, ro, rd);
+            float tm = kMaxFloat;
+            if (P.tmax) tm = P.tmax[e];
+            // t_max: positive or +inf, tested on its bits (NaN, zero and negative values fail, whatever
+            // the denormal mode); +inf is clamped to kMaxFloat
+            const int32_t tb = __float_as_int(tm);
+            ok = ray_ok(ro, rd) && tb > 0 && tb <= 0x7F800000;
+            if (ok) { o = ro; d = rd; T = fminf(tm, kMaxFloat); }  // else the placeholder: an inactive lane
+        }
+        // nothing can be accepted in (kTol, T) when T <= kTol: valid, visible, not walked
+        bool active = ok && T > kTol;
+        bool occ = active && occluded_analytic(S, o, d, T);
+        active = active && !occ;
+        if (occluded_models<LANE>(S, o, d, T, active, err, ct)) occ = true;
+        if (in) {
+            if (ok) traced += 1;
+            P.out[e] = uint8_t(!ok ? ATR_OCCL_INVALID : occ ? ATR_OCCL_OCCLUDED : ATR_OCCL_VISIBLE);
+        }
+    }
+    if (P.traced_rays) add_traced(P.traced_rays, traced, int(blockIdx.x * 4 + (threadIdx.x >> 6)));
+    if (err && P.error_flag) atomicOr(P.error_flag, 1);
+}
+
+template __global__ void ray_occlusion_kernel<false, false>(OcclParams);
+template __global__ void ray_occlusion_kernel<false, true>(OcclParams);
+template __global__ void ray_occlusion_kernel<true, false>(OcclParams);
+template __global__ void ray_occlusion_kernel<true, true>(OcclParams);
+
+}  // namespace atr
+
+// Persistent, sized like the ray query's launch: `ncu` x occupancy workgroups (4 waves each), at
+// most one wave per 64 rays.
+extern "C" hipError_t atr_launch_occlusion(const atr::OcclParams& P, int lane, int ncu, hipStream_t s) {
+    const uint64_t need = (uint64_t(P.n) + 255u) / 256u;
+    const dim3 g(unsigned(std::min<uint64_t>(uint64_t(ncu) * atr::kOcclOcc, need))), b(256);
+    const bool sort = P.perm != nullptr;
+    if (lane) {
+        if (sort) hipLaunchKernelGGL((atr::ray_occlusion_kernel<true, true>), g, b, 0, s, P);
+        else hipLaunchKernelGGL((atr::ray_occlusion_kernel<true, false>), g, b, 0, s, P);
+    } else {
+        if (sort) hipLaunchKernelGGL((atr::ray_occlusion_kernel<false, true>), g, b, 0, s, P);
+        else hipLaunchKernelGGL((atr::ray_occlusion_kernel<false, false>), g, b, 0, s, P);
+    }
+    return hipGetLastError();
+}

@@ -64,10 +64,13 @@ __device__ __forceinline__ bool scan_leaf_lane(const Ray& r, const DModel& m, ui
 
 // get_ray_kd_tree_intersection (kd_tree.cpp:302-335) for one lane: DFS passes into an LDS leaf
 // buffer (a lane-private column, 64 B per lane), sorted leaves scanned in order, stop after the
-// first leaf that improved the hit (:457-460).
+// first leaf that improved the hit (:457-460). t0: the bound the walk starts from (the reference's
+// *td.closest): kMaxFloat for the closest hit; an occlusion query's t_max (occlusion.hip), whose walk
+// then ends at the first leaf with a hit below it and leaves h.t < t0 iff there is one.
 template <bool COUNT, int K = kLeafBuf>
-__device__ __forceinline__ void tree_closest_lane(const Ray& r, const DModel& m, Hit& h, int& err, Ctr& ct) {
-    h.t = kMaxFloat;
+__device__ __forceinline__ void tree_closest_lane(const Ray& r, const DModel& m, Hit& h, int& err, Ctr& ct,
+                                                  float t0 = kMaxFloat) {
+    h.t = t0;
     h.face = 0;
     h.u = h.v = 0.f;
     const NodeBox root = load_node(m.nodes, 0);
@@ -385,11 +388,17 @@ struct FlatQ {
     bool done, need, more, rewalk;
 };
 
-template <bool COUNT, int K = kLeafBuf, bool UV = true>
-__device__ __forceinline__ FlatQ flat_begin(const Ray& r, const DModel& m, bool active, int w, int ln, Ctr& ct) {
+// SEED (an occlusion query, occlusion.hip): the lane's key starts at `start` = bits(t_max) << 32
+// instead of kKeyInit, here and at every leaf step: the scan's exclusion bound is t_max from the
+// first cluster on, a candidate with t == t_max never compares below it (low word 0), and "this leaf
+// improved" is key != start. Without SEED `start` is not read.
+template <bool COUNT, int K = kLeafBuf, bool UV = true, bool SEED = false>
+__device__ __forceinline__ FlatQ flat_begin(const Ray& r, const DModel& m, bool active, int w, int ln, Ctr& ct,
+                                            unsigned long long start = kKeyInit) {
     FlatLds<K, UV>& L = flat_lds<K, UV>();
     FlatQ q{0, 0, true, false, false, false};
-    L.key[w][ln] = kKeyInit;
+    if constexpr (SEED) L.key[w][ln] = start;
+    else L.key[w][ln] = kKeyInit;
     if (active) {
         const NodeBox root = load_node(m.nodes, 0);
         if constexpr (COUNT) { ct.box += 1; ct.box_all += 1; }
@@ -466,10 +475,12 @@ __device__ __forceinline__ void flat_pass(const Ray& r, const DModel& m, int w, 
 // sequence of bounds, and with it every output and counter of a lane-private step, is what it was
 // (DESIGN.md §4b). Leaves of more than 32 clusters keep them all (sv all ones: survivor j is
 // cluster j).
-template <bool COUNT, bool HYB, bool UO, bool NUV, int K = kLeafBuf, bool PADS = false, bool WCULL = false>
+// SEED, start: as in flat_begin.
+template <bool COUNT, bool HYB, bool UO, bool NUV, int K = kLeafBuf, bool PADS = false, bool WCULL = false,
+          bool SEED = false>
 __device__ __forceinline__ void flat_leaf_step(const Ray& r, const DModel& m, int w, int ln, bool live, FlatQ& q,
                                                Ctr& ct, int32_t hyb_a, int32_t hyb_b, const float2_t* pads = nullptr,
-                                               float hv = 0.f) {
+                                               float hv = 0.f, unsigned long long start = kKeyInit) {
     static_assert(!PADS || UO, "the table holds one origin per camera");
     static_assert(!WCULL || (UO && K >= 2), "the hull is of one origin's directions; sv's LDS slot");
     FlatLds<K, !NUV>& L = flat_lds<K, !NUV>();
@@ -527,7 +538,8 @@ __device__ __forceinline__ void flat_leaf_step(const Ray& r, const DModel& m, in
     const uint32_t incl = wave_incl_add(cn);  // inclusive prefix sum over the lanes
     const uint32_t excl = incl - cn;
     const uint32_t total = uint32_t(__builtin_amdgcn_readlane(int(incl), 63));
-    if (live) L.key[w][ln] = kKeyInit;
+    if constexpr (SEED) { if (live) L.key[w][ln] = start; }
+    else { if (live) L.key[w][ln] = kKeyInit; }
     bool deal = true;
     if constexpr (HYB) {
         // the largest cluster count of the step (counts are small: the signed max is exact)
@@ -596,7 +608,10 @@ __device__ __forceinline__ void flat_leaf_step(const Ray& r, const DModel& m, in
     }
     ATR_PCLK(if (deal) ct.t_deal += uint32_t(clock64() - tc1));
     if (live) {  // stop at the first leaf that improved the hit (kd_tree.cpp:457-460)
-        if (L.key[w][ln] != kKeyInit) {
+        bool improved;
+        if constexpr (SEED) improved = L.key[w][ln] != start;
+        else improved = L.key[w][ln] != kKeyInit;
+        if (improved) {
             q.done = true;
         } else if (++q.j >= q.nb) {
             if (q.more) q.need = q.rewalk = true;  // the next K leaves after this buffer's last

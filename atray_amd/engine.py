@@ -36,6 +36,8 @@ ATR_SAMPLES_CONVERGED = 0x80000000  # sample_count bit 31: the pixel has stopped
 MAX_FLOAT = np.float32(3.402823466e38)
 # atr_trace_rays: what a ray met (atr_ray_hits.kind)
 ATR_RAY_SKY, ATR_RAY_TRI, ATR_RAY_SPHERE, ATR_RAY_PLANE, ATR_RAY_INVALID = 0, 1, 2, 3, 4
+# atr_occluded_rays: the byte of a ray
+ATR_OCCL_VISIBLE, ATR_OCCL_OCCLUDED, ATR_OCCL_INVALID = 0, 1, 2
 
 ERRORS = {-1: "ATR_E_INVALID", -2: "ATR_E_IO", -3: "ATR_E_NOMEM", -4: "ATR_E_NOSCENE",
           -5: "ATR_E_TREE_DEPTH", -6: "ATR_E_TREE_LAYOUT"}
@@ -125,7 +127,7 @@ EXPORTS = [
     "atr_unpack_masked_ranks",
     "atr_render_plan_info", "atr_workspace_info", "atr_render_start_samples",
     "atr_render_start_adaptive", "atr_render_adaptive_info", "atr_render_cull_counters",
-    "atr_trace_rays",
+    "atr_trace_rays", "atr_occluded_rays",
 ]
 # the diagnostic build's extra symbols (include/atray_diag.h; make -C atray_amd/csrc DIAG=1)
 DIAG_EXPORTS = ["atr_render_wave_trace", "atr_render_phase_clocks", "atr_render_path_counters",
@@ -180,6 +182,7 @@ def lib():
                                        C.c_float], C.c_int),
         "atr_render_adaptive_info": ([vp, i64 * 4], C.c_int),
         "atr_trace_rays": ([vp, vp, vp, i64, P(atr_ray_hits), i32, i32, vp], C.c_int),
+        "atr_occluded_rays": ([vp, vp, vp, vp, i64, vp, vp, i32, i32, vp], C.c_int),
         "atr_render_packed_size": ([vp, i32], i64),
         "atr_render_counters": ([vp, P(atr_camera), vp, i32, C.c_uint64, i32, i64 * 10], C.c_int),
         "atr_render_cull_counters": ([vp, P(atr_camera), vp, i32, C.c_uint64, i32, i64 * 5], C.c_int),
@@ -432,6 +435,29 @@ def camera(width, height, spp=1, bounces=1, aa=False, eye=(0.1, 2.0, 0.0),
     return cm
 
 
+def segment_rays(p, q, margin=1e-3):
+    """The shadow rays of the segments p -> q for occluded_rays: (orig, dirs, t_max) with v = q - p,
+    len = sqrt(len2(v)), dirs = v * (1 / len), t_max = len * (1 - margin). Pure torch (CPU or device
+    tensors, (n, 3) float32); every step a separately rounded f32 operation in engine.h's order
+    (len2 = (x*x + y*y) + z*z), so a non-degenerate segment passes the query's 2^-20 validity test.
+    p == q gives a NaN direction, hence ATR_OCCL_INVALID. The margin keeps the surface at q itself
+    out of the window."""
+    import torch
+    for name, a in (("p", p), ("q", q)):
+        if not isinstance(a, torch.Tensor) or a.dtype != torch.float32 or a.dim() != 2 or a.shape[1] != 3:
+            raise ValueError(f"{name}: an (n, 3) float32 tensor is required")
+    if p.shape != q.shape:
+        raise ValueError("p and q differ in length")
+    v = q - p
+    x, y, z = v[:, 0], v[:, 1], v[:, 2]
+    # the correctly rounded f32 square root: through f64 (rounding its 53-bit root to 24 bits is
+    # exact rounding); torch's vectorised f32 sqrt on the CPU is not correctly rounded
+    length = torch.sqrt(((x * x + y * y) + z * z).double()).float()
+    inv = torch.ones_like(length) / length
+    keep = torch.ones_like(length) - torch.full_like(length, float(margin))
+    return p, v * inv[:, None], length * keep
+
+
 class Engine:
     """One device context (atr_ctx): scene upload + renders on a HIP stream."""
 
@@ -547,6 +573,51 @@ class Engine:
                                    C.c_void_p(dirs.data_ptr()) if n else None, n, C.byref(hits), int(variant),
                                    int(sort_bits), C.c_void_p(stream) if stream else None), "trace rays")
         return out, traced
+
+    def occluded_rays(self, orig, dirs, t_max=None, variant=ATR_KERNEL_AUTO, sort_bits=-1, stream=None):
+        """atr_occluded_rays: for every ray of a batch, is there any hit with 1e-4 < t < t_max. orig,
+        dirs: as for trace_rays; t_max: a contiguous (n,) float32 tensor on the engine's device, or None
+        (every ray unbounded). Returns (a uint8 tensor of ATR_OCCL_* in input order, the traced-ray count
+        as a one-element int64 tensor); valid once the stream has run, e.g. after wait()."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        for name, a in (("orig", orig), ("dirs", dirs)):
+            if not isinstance(a, torch.Tensor) or a.dtype != torch.float32 or a.dim() != 2 or a.shape[1] != 3:
+                raise ValueError(f"{name}: an (n, 3) float32 tensor is required")
+            if a.device != dev:
+                raise ValueError(f"{name}: not on {dev}")
+            if not a.is_contiguous():
+                raise ValueError(f"{name}: not contiguous")
+        if orig.shape[0] != dirs.shape[0]:
+            raise ValueError("orig and dirs differ in length")
+        n = int(orig.shape[0])
+        if t_max is not None:
+            if not isinstance(t_max, torch.Tensor) or t_max.dtype != torch.float32 or t_max.dim() != 1:
+                raise ValueError("t_max: an (n,) float32 tensor is required")
+            if t_max.device != dev:
+                raise ValueError(f"t_max: not on {dev}")
+            if not t_max.is_contiguous():
+                raise ValueError("t_max: not contiguous")
+            if t_max.shape[0] != n:
+                raise ValueError("t_max and orig differ in length")
+        occ = torch.empty(n, dtype=torch.uint8, device=dev)
+        traced = torch.zeros(1, dtype=torch.int64, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        check(lib().atr_occluded_rays(self.h, C.c_void_p(orig.data_ptr()) if n else None,
+                                      C.c_void_p(dirs.data_ptr()) if n else None,
+                                      C.c_void_p(t_max.data_ptr()) if n and t_max is not None else None, n,
+                                      C.c_void_p(occ.data_ptr()) if n else None, C.c_void_p(traced.data_ptr()),
+                                      int(variant), int(sort_bits), C.c_void_p(stream) if stream else None),
+              "occluded rays")
+        return occ, traced
+
+    def occluded_segments(self, p, q, margin=1e-3, variant=ATR_KERNEL_AUTO, sort_bits=-1, stream=None):
+        """Is the segment from p towards q blocked before it reaches q: segment_rays, then occluded_rays
+        (p == q comes back as ATR_OCCL_INVALID). p, q: (n, 3) float32 tensors on the engine's device."""
+        orig, dirs, t_max = segment_rays(p, q, margin)
+        return self.occluded_rays(orig.contiguous(), dirs.contiguous(), t_max.contiguous(), variant=variant,
+                                  sort_bits=sort_bits, stream=stream)
 
     def adaptive_info(self):
         """The last adaptive pass's counts, once wait() returned 0: (pixels live at its start, blocks

@@ -26,7 +26,7 @@ extern "C" {
 /* ABI 2 (round 6): atr_tuning gained reserved[4] (zero; room for later knobs without a size
    change); ABI 1's last two words became path_sort_bits and path_split in round 5.
    atr_trace_rays and atr_ray_hits were added since without a version change: no existing struct
-   or entry point changed. */
+   or entry point changed. atr_occluded_rays likewise. */
 #define ATR_ABI_VERSION 2
 
 enum {
@@ -499,6 +499,42 @@ typedef struct {           /* DEVICE pointers, one element per ray, input order;
 } atr_ray_hits;
 int atr_trace_rays(atr_ctx* ctx, const float* origins, const float* directions, int64_t nrays,
                    const atr_ray_hits* hits, int32_t variant, int32_t sort_bits, void* stream);
+
+/* Occlusion queries (shadow rays, visibility between points): is there ANY hit with
+   1e-4 < t < t_max along the ray (strict on both sides)? One byte per ray, no hit record.
+   It is the reference's own traversal with its closest distance started at the ray's t_max instead
+   of MAX_FLOAT -- how a user of the reference would cast a shadow ray. With T the ray's t_max:
+     tree models   the walk of get_ray_kd_tree_intersection (root box; the root leaf, or the DFS with
+                   its nodes_hit <= 4 loop and the leaves scanned in ascending distance) with closest
+                   = T; the model occludes iff some leaf's scan improves on T, i.e. iff some triangle
+                   of some leaf that walk reaches has 1e-4 < t < T. A leaf whose hits are all >= T does
+                   not end the walk (closest-hit's stop at the first leaf that holds any hit does not
+                   apply to hits that do not count).
+     brute-force   the surrounding box test, then any face.
+     spheres, planes  the reference's tests with the same window.
+   The answer does not depend on the order of models or leaves. Triangles are tested with the
+   reference's CULLED test: a back-facing triangle does not occlude, so the rays p->q and q->p can
+   differ. Consequences (both tested):
+     - with t_max NULL or 3.402823466e38, occluded == (atr_trace_rays' t < 3.402823466e38);
+     - for any t_max, atr_trace_rays' t < t_max implies occluded. The converse fails only where
+       closest-hit's first-hit-leaf rule kept a farther hit and hid a nearer one in a later leaf; there
+       this query is the geometrically right one.
+   origins, directions: as for atr_trace_rays (DEVICE, 3 floats per ray, the same validity test).
+   t_max: DEVICE, one float per ray, or NULL = every ray unbounded (3.402823466e38). +inf counts as
+   3.402823466e38; NaN, zero or negative makes the ray invalid; 0 < t_max <= 1e-4 is valid and
+   VISIBLE (nothing can be accepted below the tolerance). An invalid ray (direction, origin or t_max)
+   gets ATR_OCCL_INVALID, is not traced and does not count in traced_rays; no NaN reaches the traversal.
+   occluded: DEVICE, one byte per ray (ATR_OCCL_*), written at the ray's input index; required when
+   nrays > 0. traced_rays: optional DEVICE accumulator, += the valid rays.
+   variant: ATR_KERNEL_AUTO and ATR_KERNEL_FLAT = the clustered scan with its exclusion bound started
+   at t_max, ATR_KERNEL_LANE = the per-lane reference scan; the same bytes; else ATR_E_INVALID.
+   sort_bits, stream, atr_render_wait, atr_last_kernel_ms, the query workspace, nrays == 0, the
+   argument errors and ATR_E_NOSCENE: exactly as for atr_trace_rays. No output byte depends on
+   sort_bits. No struct and no ABI version change. */
+enum { ATR_OCCL_VISIBLE = 0, ATR_OCCL_OCCLUDED = 1, ATR_OCCL_INVALID = 2 };
+int atr_occluded_rays(atr_ctx* ctx, const float* origins, const float* directions, const float* t_max,
+                      int64_t nrays, uint8_t* occluded, unsigned long long* traced_rays,
+                      int32_t variant, int32_t sort_bits, void* stream);
 
 /* wait_for_render_from_camera_to_finish: 1 = still running after timeout_ms, 0 = done,
    <0 = error. tiles_done (optional) = tiles of the last render known complete (progress). */
