@@ -1364,6 +1364,23 @@ int atr_scene_upload(atr_ctx* c, const atr_material* mats, int32_t nmats, const 
                 if (d >= kMaskLevels) return ATR_E_TREE_DEPTH;
         }
     }
+    // Every check of the input that can fail runs before the old scene is freed: a rejected upload
+    // leaves the context as it was. The trees are packed here (pack_tree reports ATR_E_TREE_LAYOUT
+    // and the index errors of a caller-made tree), the brute-force models' face indices checked.
+    std::vector<PackedTree> packed(size_t(nmodels), PackedTree{});
+    int64_t total_clusters = 0;
+    for (int32_t i = 0; i < nmodels; ++i) {
+        const atr_model& md = models[i];
+        if (md.tree) {
+            if (const int rc = pack_tree(md.tree->t, c->tune.cluster_size, packed[size_t(i)])) return rc;
+            total_clusters += int64_t(packed[size_t(i)].nclusters);
+            if (total_clusters > int64_t(UINT32_MAX)) return ATR_E_INVALID;
+        } else {
+            const HostMesh& M = md.mesh->m;
+            for (int32_t vi : M.face_v)
+                if (vi < 0 || size_t(vi) >= M.vertices.size()) return ATR_E_INVALID;
+        }
+    }
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(wait_all(c));  // kernels on any stream may still read the old scene
     free_scene(c);
@@ -1434,8 +1451,8 @@ int atr_scene_upload(atr_ctx* c, const atr_material* mats, int32_t nmats, const 
         dm.shade = static_cast<const float*>(p);
         if (md.tree) {
             const HostTree& T = md.tree->t;
-            PackedTree PT;  // every device table of the model (host_scene.cpp pack_tree)
-            if ((rc = pack_tree(T, c->tune.cluster_size, PT))) return rc;
+            // every device table of the model (host_scene.cpp pack_tree), packed above; dropped after this model
+            PackedTree PT = std::move(packed[size_t(i)]);
             c->max_depth = std::max(c->max_depth, PT.max_depth);
             auto up = [&](const auto& v, auto*& dst) {
                 void* q = nullptr;

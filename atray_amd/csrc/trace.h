@@ -404,7 +404,11 @@ __device__ __forceinline__ uint32_t examine_inner(const Ray& r, const Inner& n, 
             if (in) {
                 ++nodes_hit;
                 const float tx = tzmax < tmax ? tzmax : tmax;
-                if (!(cull && (tx <= 0.0f || tx < bd))) mask |= 1u << i;
+                // Instrumented builds walk the subtrees behind the origin on the first pass, as the
+                // reference does: ct.box is then its box-test count for an origin inside the tree too
+                // (no leaf below is inserted, see above: the outputs and the leaf counts are the same).
+                const bool behind = (!COUNT || !first_pass) && tx <= 0.0f;
+                if (!(cull && (behind || tx < bd))) mask |= 1u << i;
             }
         } else {  // leaf child: get_ray_AABB_intersection (aabb.h:29-63)
             if (tzmin > tmin) tmin = tzmin;

@@ -207,7 +207,9 @@ int atr_set_tuning(atr_ctx* ctx, const atr_tuning* tuning);
 int atr_get_tuning(atr_ctx* ctx, atr_tuning* out);
 
 /* Flatten + upload the scene (copies; the caller keeps its buffers). prep_scene's tree build
-   happens before this call (atr_octree_build); upload is not part of the render timing. */
+   happens before this call (atr_octree_build); upload is not part of the render timing.
+   An upload rejected for its input (ATR_E_INVALID, ATR_E_TREE_DEPTH, ATR_E_TREE_LAYOUT) is
+   rejected as a whole and leaves the scene uploaded before in place. */
 int atr_scene_upload(atr_ctx* ctx, const atr_material* materials, int32_t nmaterials,
                      const atr_model* models, int32_t nmodels, const atr_sphere* spheres,
                      int32_t nspheres, const atr_plane* planes, int32_t nplanes);

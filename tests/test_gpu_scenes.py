@@ -30,7 +30,7 @@ W, H = 96, 72
 # part name -> (asset, centre, leaf size, tree?)
 PARTS = {
     "cube": ("Cube", CENTERS["Cube"], 300, True),              # 12 faces: the root is a leaf
-    "monkey": ("Monkey", CENTERS["Monkey"], 64, True),          # smooth normals, a deep tree
+    "monkey": ("Monkey", CENTERS["Monkey"], 64, True),          # smooth normals, a tree of depth 5
     "deer": ("Deer", CENTERS["Deer"], 300, True),               # no normals: flat shading
     "cube_bf": ("Cube", (1.3, 0.5, -3.2), 300, False),          # brute force, overlapping the others
     "cube_in_monkey": ("Cube", CENTERS["Monkey"], 300, True),   # around the Monkey, which only its ears leave
