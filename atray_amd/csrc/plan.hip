@@ -66,8 +66,8 @@ __device__ __forceinline__ int block_class(const Thresholds& T, int bkt) {
     return k;
 }
 
-// a zeroed Thresholds (the first plan) gives class 0 and one wave to every cell: split thresholds
-// of 0 are replaced by "no split" (kPlanBuckets) when derived, so 0 only occurs before the first
+// a zeroed Thresholds (the first plan) gives class 0 and one wave to every cell: a derived split
+// threshold of 0 is stored as 1 ("no split" is kPlanBuckets), so 0 only occurs before the first
 __device__ __forceinline__ int block_parts(const Thresholds& T, int bkt) {
     if (T.split_thr == 0) return 1;
     return bkt >= T.split4_thr ? 4 : (bkt >= T.split_thr ? 2 : 1);
