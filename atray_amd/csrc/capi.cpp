@@ -20,56 +20,12 @@
 
 #include "engine.h"
 #include "host_scene.h"
+#include "launch.h"
 #ifdef ATR_DIAG
 #include "../../include/atray_diag.h"
 #endif
 
 using namespace atr;
-
-extern "C" hipError_t atr_launch_render(const atr::RenderParams& P, int sched, int primary_occ, hipStream_t s);
-extern "C" int atr_render_reads_pads(const atr::RenderParams& P, int sched);
-extern "C" hipError_t atr_launch_camera_pads(const atr::DScene* scene, const atr::PadEyes& eyes, int32_t nrows,
-                                             int32_t stride, atr::float2_t* table, hipStream_t s);
-extern "C" hipError_t atr_launch_traced_finish(unsigned long long* slots, unsigned long long* out, hipStream_t s);
-extern "C" hipError_t atr_launch_unpack(const atr::DBlock* blocks, int32_t nblocks, int32_t width,
-                                        const uint32_t* packed, uint32_t* image, hipStream_t s);
-extern "C" hipError_t atr_launch_path_camera(const atr::PathParams& P, int occ, hipStream_t s);
-extern "C" hipError_t atr_launch_path_bounce(const atr::PathParams& P, int ncu, int occ, hipStream_t s);
-extern "C" hipError_t atr_launch_path_resolve(const atr::PathParams& P, hipStream_t s);
-extern "C" hipError_t atr_launch_path_sort(const atr::PathParams& P, int ncu, hipStream_t s);
-extern "C" hipError_t atr_launch_path_live(const atr::PathParams& P, hipStream_t s);
-extern "C" hipError_t atr_launch_path_camera_adaptive(const atr::PathParams& P, int ncu, hipStream_t s);
-extern "C" hipError_t atr_launch_path_resolve_adaptive(const atr::PathParams& P, hipStream_t s);
-extern "C" hipError_t atr_launch_query_sort(const atr::QueryParams& P, int ncu, hipStream_t s);
-extern "C" hipError_t atr_launch_query(const atr::QueryParams& P, int lane, int ncu, hipStream_t s);
-extern "C" hipError_t atr_launch_occlusion(const atr::OcclParams& P, int lane, int ncu, hipStream_t s);
-extern "C" hipError_t atr_launch_tile_casts(const atr_tile* tiles, int32_t ntiles, int32_t width,
-                                            const uint32_t* casts, int64_t* out, hipStream_t s);
-extern "C" hipError_t atr_launch_packed_tile_casts(const int32_t* slot_tile, int64_t nslots, const uint32_t* casts,
-                                                   int64_t frame_stride, int32_t nframes, int32_t ntiles,
-                                                   unsigned long long* out, hipStream_t s);
-
-extern "C" hipError_t atr_launch_plan(const atr::DBlock* base, int32_t nb, unsigned long long* cost,
-                                      unsigned long long* cost_last, void* work, atr::DBlock* out, int32_t max_split,
-                                      float split2, float split4, hipStream_t s);
-extern "C" size_t atr_plan_work_bytes(int32_t nb);
-extern "C" hipError_t atr_launch_pack_bgr(const uint32_t* src, int64_t n, uint8_t* dst, hipStream_t s);
-extern "C" int64_t atr_masked_chunks(int64_t n);
-extern "C" int atr_unpack_max_sources();
-extern "C" hipError_t atr_launch_unpack_masked_multi(int32_t n, const atr::DBlock* const* blocks,
-                                                     const int32_t* nblocks, const int64_t* own,
-                                                     const uint8_t* const* in, const int32_t* raw, int32_t width,
-                                                     int32_t nframes, uint32_t* image, int64_t image_stride,
-                                                     hipStream_t s);
-extern "C" hipError_t atr_launch_unpack_masked(const atr::DBlock* blocks, int32_t nblocks, int32_t width,
-                                               const uint8_t* in, int32_t nframes, int64_t own, uint32_t* image,
-                                               int64_t image_stride, hipStream_t s);
-extern "C" hipError_t atr_launch_pack_bgr_masked(const uint32_t* src, int64_t n, uint32_t bg, uint8_t* out,
-                                                 int64_t* nbytes, hipStream_t s);
-extern "C" hipError_t atr_launch_scatter_bgr_masked(const uint8_t* in, int64_t n, const int64_t* dst_index,
-                                                    uint32_t* image, hipStream_t s);
-extern "C" hipError_t atr_launch_scatter_bgr(const uint8_t* src, int64_t n, const int64_t* dst_index,
-                                             uint32_t* image, hipStream_t s);
 
 #define HIPCHK(x)                                      \
     do {                                               \

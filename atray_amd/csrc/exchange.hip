@@ -8,7 +8,7 @@
 #include <stdint.h>
 #include <cstring>
 
-#include "engine.h"
+#include "launch.h"
 
 namespace atr {
 

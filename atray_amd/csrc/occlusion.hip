@@ -4,51 +4,19 @@
 //   ray_occlusion_kernel  persistent waves claim 64 positions of the batch at a time (the batch's
 //                         key order comes from query.hip's ray_query_keys / ray_query_rank), test
 //                         the spheres and planes, then the models in upload order with the scan's
-//                         bound seeded at t_max (scan.h SEED; LANE: the per-lane reference scan
-//                         started at t_max); a lane retires at its first hit, the model loop ends
-//                         when no lane of the wave is left.
+//                         bound seeded at t_max (scan.h flat_query in FlavOcclusion; LANE: the
+//                         per-lane reference scan started at t_max); a lane retires at its first
+//                         hit, the model loop ends when no lane of the wave is left.
 // A file of its own: the render, path and ray-query kernels' code objects are what they were.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
+#include "launch.h"
 #include "scan.h"
+#include "sort_key.h"
 
 namespace atr {
-
-__device__ __forceinline__ void load_ray(const float* __restrict__ po, const float* __restrict__ pd, uint32_t e, V3& o,
-                                         V3& d) {
-    const size_t b = 3 * size_t(e);
-    o = mk(po[b], po[b + 1], po[b + 2]);
-    d = mk(pd[b], pd[b + 1], pd[b + 2]);
-}
-
-// The t of shade.h's sphere and plane tests (sphere.h:12-39, plane.h:12-22), the same f32 operations
-// in the same order; 0: no hit.
-__device__ __forceinline__ float sphere_t(V3 o, V3 d, const DSphere& sp) {
-    const V3 pc = sub(o, mk(sp.cx, sp.cy, sp.cz));
-    const float pcs = len2(pc);
-    const float b = 2 * (dot(d, pc));
-    const float bs = b * b;
-    const float c = pcs - sp.r * sp.r;
-    const float dmt = bs - (4 * c);
-    float t = 0;
-    if (!(dmt < 0)) {
-        const float ta = (-b + sqrtf(dmt)) * 0.5f;
-        const float tb = (-b - sqrtf(dmt)) * 0.5f;
-        if (ta <= 0 && tb <= 0) t = 0;
-        else if (tb > 0) t = tb;
-        else t = ta;
-    }
-    return t;
-}
-__device__ __forceinline__ float plane_t(V3 o, V3 d, const DPlane& pl) {
-    const V3 n = mk(pl.nx, pl.ny, pl.nz);
-    const float denom = dot(n, d);
-    float t = 0;
-    if (!(denom > -kTol && denom < kTol)) t = (pl.d - dot(o, n)) / denom;
-    return t;
-}
 
 // Any sphere or plane with kTol < t < T (every lane of the wave; the counts are wave-uniform).
 __device__ __forceinline__ bool occluded_analytic(const DScene* __restrict__ S, V3 o, V3 d, float T) {
@@ -70,8 +38,9 @@ __device__ __forceinline__ bool occluded_analytic(const DScene* __restrict__ S, 
 // inactive for the models after it, and the loop ends once no lane is left. Tree models: the
 // reference's walk (root box, root leaf or the DFS's leaves in ascending distance) with its closest
 // started at T, which ends at the first leaf that improves on it. LANE: the per-lane reference scan;
-// otherwise the clustered scan in the bounce flavour without barycentrics (near-first passes into the
-// LDS leaf buffer, every step dealt, no u/v rows in LDS), the key seeded with T.
+// otherwise the clustered scan's query loop (scan.h flat_query) in FlavOcclusion -- the bounce flavour
+// without barycentrics (near-first passes into the LDS leaf buffer, every step dealt, no u/v rows in
+// LDS), the key seeded with T -- and "the key moved" in place of the closest hit's read-out.
 template <bool LANE>
 __device__ __forceinline__ bool occluded_models(const DScene* __restrict__ S, V3 o, V3 d, float T, bool active, int& err,
                                                 Ctr& ct) {
@@ -90,17 +59,10 @@ __device__ __forceinline__ bool occluded_models(const DScene* __restrict__ S, V3
                     hit = h.t < T;
                 }
             } else {
-                constexpr int K = kLeafBuf;
                 const int w = threadIdx.x >> 6, ln = threadIdx.x & 63;
                 const unsigned long long start = static_cast<unsigned long long>(__float_as_uint(T)) << 32;
-                FlatQ q = flat_begin<false, K, false, true>(r, m, active, w, ln, ct, start);
-                for (;;) {
-                    flat_pass<false, true, false, true, K, false>(r, m, w, ln, q, err, ct);
-                    if (__ballot(!q.done) == 0) break;
-                    flat_leaf_step<false, false, false, true, K, false, false, true>(r, m, w, ln, !q.done, q, ct, 0, 0,
-                                                                                     nullptr, 0.f, start);
-                }
-                hit = active && flat_lds<K, false>().key[w][ln] != start;
+                flat_query<FlavOcclusion, false>(r, m, active, w, ln, err, ct, 0, 0, nullptr, 0, start);
+                hit = active && flat_lds<kLeafBuf, FlavOcclusion::UV>().key[w][ln] != start;
             }
         } else if (active) {  // brute force: the surrounding box, then the faces up to the first hit
             if (box_entry(r, m.aabb[0], m.aabb[1], m.aabb[2], m.aabb[3], m.aabb[4], m.aabb[5]) != 0) {

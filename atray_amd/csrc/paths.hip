@@ -22,6 +22,7 @@
 // bounces and resolve per batch on one stream (capi.cpp launch_paths).
 #include <hip/hip_runtime.h>
 
+#include "launch.h"
 #include "scan.h"
 #include "sort_key.h"
 
@@ -165,7 +166,7 @@ __global__ __launch_bounds__(256, OCC) void path_camera_kernel(PathParams P) {
     Ctr ct;
     Isect id;
     id.type = T_NONE;
-    intersect_scene<SCHED_HYBRID, FLAV_CAMERA, COUNT>(S, eye, d, active, id, err, ct, P.hyb_a, P.hyb_b);
+    intersect_scene<SCHED_HYBRID, FlavCamera, COUNT>(S, eye, d, active, id, err, ct, P.hyb_a, P.hyb_b);
     bool go = false;
     V3 o = eye, ret = mk(0.f, 0.f, 0.f), w = mk(1.f, 1.f, 1.f);
     if (active) {
@@ -230,7 +231,7 @@ __global__ __launch_bounds__(256, OCC) void path_bounce_kernel(PathParams P) {
             o = mk(a.x, a.y, a.z);
             d = mk(a.w, b.x, b.y);
         }
-        const SceneHit sh = intersect_models<SCHED_FLAT, FLAV_BOUNCE, COUNT, kBounceLeafBuf>(S, o, d, valid, err, ct, P.hyb_a, P.hyb_b);
+        const SceneHit sh = intersect_models<SCHED_FLAT, FlavBounce, COUNT, kBounceLeafBuf>(S, o, d, valid, err, ct, P.hyb_a, P.hyb_b);
         // the path -- its ray too -- is read again after the query instead of being held through
         // it: the memory clobber keeps the loads here, the opaque copy of the entry index keeps
         // their addresses from being formed before the query
@@ -560,7 +561,7 @@ __global__ __launch_bounds__(256, 6) void path_camera_adaptive_kernel(PathParams
         Ctr ct;
         Isect id;
         id.type = T_NONE;
-        intersect_scene<SCHED_HYBRID, FLAV_CAMERA, false>(S, eye, d, active, id, err, ct, P.hyb_a, P.hyb_b);
+        intersect_scene<SCHED_HYBRID, FlavCamera, false>(S, eye, d, active, id, err, ct, P.hyb_a, P.hyb_b);
         bool go = false;
         V3 o = eye, ret = mk(0.f, 0.f, 0.f), w = mk(1.f, 1.f, 1.f);
         if (active) {

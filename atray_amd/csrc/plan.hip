@@ -15,7 +15,7 @@
 // consecutive frames); the order itself always follows the latest costs.
 #include <hip/hip_runtime.h>
 
-#include "engine.h"
+#include "launch.h"
 
 #ifndef ATR_PLAN_SPLIT2
 #define ATR_PLAN_SPLIT2 0.01f

@@ -13,17 +13,11 @@
 
 #include <algorithm>
 
+#include "launch.h"
 #include "scan.h"
 #include "sort_key.h"
 
 namespace atr {
-
-__device__ __forceinline__ void load_ray(const float* __restrict__ po, const float* __restrict__ pd, uint32_t e, V3& o,
-                                         V3& d) {
-    const size_t b = 3 * size_t(e);
-    o = mk(po[b], po[b + 1], po[b + 2]);
-    d = mk(pd[b], pd[b + 1], pd[b + 2]);
-}
 
 // Key and arrival rank per ray (grid-stride, a wavefront takes 64 consecutive rays). kr and hist as
 // in the path engine's queue sort, but the lanes of a wave that share a key arrive together: the
@@ -119,8 +113,8 @@ __global__ __launch_bounds__(256, kQueryOcc) void ray_query_kernel(QueryParams P
             if (ok) { o = ro; d = rd; }  // a ray that fails keeps the placeholder: an inactive lane
         }
         SceneHit sh;
-        if constexpr (LANE) sh = intersect_models<SCHED_LANE, FLAV_BOUNCE, false>(S, o, d, ok, err, ct, P.hyb_a, P.hyb_b);
-        else sh = intersect_models<SCHED_FLAT, FLAV_BOUNCE, false>(S, o, d, ok, err, ct, P.hyb_a, P.hyb_b);
+        if constexpr (LANE) sh = intersect_models<SCHED_LANE, FlavBounce, false>(S, o, d, ok, err, ct, P.hyb_a, P.hyb_b);
+        else sh = intersect_models<SCHED_FLAT, FlavBounce, false>(S, o, d, ok, err, ct, P.hyb_a, P.hyb_b);
         // the ray is read again after the query instead of being held through it (as the bounce
         // kernel does): the memory clobber keeps the loads here, the opaque copy of the index keeps
         // their addresses from being formed before the query
@@ -171,7 +165,6 @@ template __global__ void ray_query_kernel<true, true>(QueryParams);
 }  // namespace atr
 
 // The batch's key order into P.sort.perm (the bins zero before and after).
-extern "C" hipError_t atr_launch_sort_bins(const atr::PathSort& so, hipStream_t s);
 extern "C" hipError_t atr_launch_query_sort(const atr::QueryParams& P, int ncu, hipStream_t s) {
     const unsigned grid = unsigned(std::min<uint64_t>(uint64_t(ncu) * 16u, (uint64_t(P.n) + 255u) / 256u));
     hipLaunchKernelGGL(atr::ray_query_keys, dim3(grid), dim3(256), 0, s, P);

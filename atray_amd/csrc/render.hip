@@ -9,6 +9,7 @@
 // leaf steps, ...) were removed in round 4; git history keeps them ("Removed").
 #include <hip/hip_runtime.h>
 
+#include "launch.h"
 #include "scan.h"
 
 namespace atr {
@@ -64,13 +65,13 @@ __device__ __forceinline__ V3 cast_ray(const DScene* __restrict__ S, V3 o, V3 d,
             if constexpr (PRIV) __asm__ volatile("" ::"s"(pstash) : "memory");
             __asm__ volatile("" ::: "memory");  // the values below come back from memory
         }
-        if constexpr (SCHED == SCHED_LANE) intersect_scene<SCHED, FLAV_BOUNCE, COUNT>(S, o, d, go, id, err, ct, hyb_a, hyb_b);
+        if constexpr (SCHED == SCHED_LANE) intersect_scene<SCHED, FlavBounce, COUNT>(S, o, d, go, id, err, ct, hyb_a, hyb_b);
         else if constexpr (SCHED == SCHED_HYBRID)
-            intersect_scene<SCHED, FLAV_HYB_BOUNCE, COUNT>(S, o, d, go, id, err, ct, hyb_a, hyb_b);
+            intersect_scene<SCHED, FlavHybBounce, COUNT>(S, o, d, go, id, err, ct, hyb_a, hyb_b);
         else if (i == 0)  // FLAT: the camera rays (one origin, coherent) take HYBRID's primary flavour
-            intersect_scene<SCHED, FLAV_CAMERA, COUNT>(S, o, d, go, id, err, ct, hyb_a, hyb_b);
+            intersect_scene<SCHED, FlavCamera, COUNT>(S, o, d, go, id, err, ct, hyb_a, hyb_b);
         else
-            intersect_scene<SCHED, FLAV_BOUNCE, COUNT>(S, o, d, go, id, err, ct, hyb_a, hyb_b);
+            intersect_scene<SCHED, FlavBounce, COUNT>(S, o, d, go, id, err, ct, hyb_a, hyb_b);
         if constexpr (STASH) {
             if constexpr (PRIV) __asm__ volatile("" ::"s"(pstash) : "memory");
             __asm__ volatile("" ::: "memory");
@@ -174,11 +175,11 @@ __global__ __launch_bounds__(256, OCC) void render_kernel(RenderParams P) {
             // the camera's row: the frame index and the stride are wave-uniform, the base stays in SGPRs
             const int32_t row = P.nfcam > 0 ? __builtin_amdgcn_readfirstlane(fidx) : 0;
             const float2_t* pads = uniform_global(P.pads) + int64_t(row) * P.pads_stride;
-            intersect_scene<SCHED, FLAV_PRIMARY_PADS, COUNT>(S, eye, dir, active, id, err, ct, P.hyb_a, P.hyb_b, pads,
-                                                             P.wave_cull);
+            intersect_scene<SCHED, FlavPrimaryPads, COUNT>(S, eye, dir, active, id, err, ct, P.hyb_a, P.hyb_b, pads,
+                                                           P.wave_cull);
         } else {
-            intersect_scene<SCHED, FLAV_PRIMARY, COUNT>(S, eye, dir, active, id, err, ct, P.hyb_a, P.hyb_b, nullptr,
-                                                        P.wave_cull);
+            intersect_scene<SCHED, FlavPrimary, COUNT>(S, eye, dir, active, id, err, ct, P.hyb_a, P.hyb_b, nullptr,
+                                                       P.wave_cull);
         }
         if (active) {
             const DMaterial& mat = S->mats[id.material];

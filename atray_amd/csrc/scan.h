@@ -4,7 +4,7 @@
 // Two bit-identical schedules of the leaf scan (the hot loop, kd_tree.cpp:437-462):
 //   LANE: every lane walks its own sorted leaves and tests every triangle of each (the reference's
 //         exact work; per-lane SoA loads);
-//   FLAT / HYBRID (tree_closest_flat): the clustered scan (cluster.h) with the
+//   FLAT / HYBRID (flat_query): the clustered scan (cluster.h) with the
 //         wavefront's (ray, cluster) work dealt over its 64 lanes, candidates compacted (§4d-§4f).
 // Shared by the cell kernels (render.hip) and the sample-parallel path kernels (paths.hip).
 #pragma once
@@ -237,13 +237,41 @@ __device__ __forceinline__ FlatLds<K, UV>& flat_lds() {
 
 constexpr unsigned long long kKeyInit = (static_cast<unsigned long long>(0x7F7FFFFFu) << 32) | 0xFFFFFFFFull;
 
+#ifndef ATR_BOUNCE_HYB  // experiment builds: 1 = the path engine's bounce rays choose lane-private or
+#define ATR_BOUNCE_HYB 0  // dealt leaf steps per step as HYBRID does (thresholds hybrid_a, hybrid_b)
+#endif
+
+// Flavours of the clustered scan: the one template argument F of every piece below. The pieces
+// explain the members they read: SEED flat_begin; UT, LDSB, NEAR flat_pass; HYB, PADS, WCULL
+// flat_leaf_step. UO: every ray of the wave has the same origin. UV: the hit's barycentrics feed an
+// output (else FlatLds has no u/v rows). EARLY: the flavour's bit of ATR_EARLY_NRM (cluster.h).
+// CAMERA rays (one origin, coherent: HYBRID's wave-walked passes, LDS leaf buffer); PRIMARY-only
+// frames (CAMERA without u and v, wave cull), PRIMARY_PADS with the table; BOUNCE rays (incoherent:
+// near-first passes into the LDS leaf buffer, every step dealt), HYB_BOUNCE the cell kernels' (register
+// leaf buffer, HYBRID's choice per step); OCCLUSION queries (BOUNCE without u and v, seeded key).
+// clang-format off
+struct FlavCamera      { static constexpr bool HYB = true,  LDSB = true,  UO = true,  UT = true,  UV = true,
+                         NEAR = false, PADS = false, WCULL = false, SEED = false; static constexpr int EARLY = 2; };
+struct FlavPrimary     { static constexpr bool HYB = true,  LDSB = true,  UO = true,  UT = true,  UV = false,
+                         NEAR = false, PADS = false, WCULL = true,  SEED = false; static constexpr int EARLY = 1; };
+struct FlavPrimaryPads { static constexpr bool HYB = true,  LDSB = true,  UO = true,  UT = true,  UV = false,
+                         NEAR = false, PADS = true,  WCULL = true,  SEED = false; static constexpr int EARLY = 8; };
+struct FlavHybBounce   { static constexpr bool HYB = true,  LDSB = false, UO = false, UT = false, UV = true,
+                         NEAR = false, PADS = false, WCULL = false, SEED = false; static constexpr int EARLY = 4; };
+struct FlavBounce      { static constexpr bool HYB = ATR_BOUNCE_HYB != 0, LDSB = true, UO = false, UT = false,
+                         UV = true, NEAR = true, PADS = false, WCULL = false, SEED = false;
+                         static constexpr int EARLY = 4; };
+struct FlavOcclusion   { static constexpr bool HYB = false, LDSB = true,  UO = false, UT = false, UV = false,
+                         NEAR = true,  PADS = false, WCULL = false, SEED = true;  static constexpr int EARLY = 1; };
+// clang-format on
+
 // One full test of candidate `slot` for the ray q of owner lane `ow`: lowers the owner's (t bits,
 // leaf rank) key in LDS -- the minimum over the leaf in any order is the reference's
 // first-in-leaf-order closest hit (kd_tree.cpp:440-456); true if this test lowered it.
-template <bool COUNT, int K = kLeafBuf, bool UV = true>
+template <class F, bool COUNT, int K = kLeafBuf>
 __device__ __forceinline__ bool cand_test(const Ray& q, const DModel& m, int w, int32_t ow, uint32_t slot,
                                           unsigned long long& mine, float& u, float& v, Ctr& ct) {
-    FlatLds<K, UV>& L = flat_lds<K, UV>();
+    FlatLds<K, F::UV>& L = flat_lds<K, F::UV>();
     if constexpr (COUNT) ct.tri += 1;
     float4_t a0, a1, a2;
     load_prim(m, slot, a0, a1, a2);
@@ -268,12 +296,11 @@ __device__ __forceinline__ bool cand_test(const Ray& q, const DModel& m, int w, 
 //               owner lookup or ray shuffles per test);
 //   compacted -- the wave's candidates are numbered by a prefix sum of the masks' popcounts and
 //               dealt 64 per sub-round, one full test per lane.
-// The winning test of each (sub-)round writes its owner's slot and barycentrics. UO: every ray of
-// the wave has the same origin (camera rays).
-template <bool COUNT, bool UO, bool NUV, bool SELF = false, int K = kLeafBuf>
+// The winning test of each (sub-)round writes its owner's slot and barycentrics.
+template <class F, bool COUNT, bool SELF, int K = kLeafBuf>
 __device__ __forceinline__ void cand_rounds(const Ray& r, const DModel& m, int w, int ln, uint32_t cm,
                                             uint32_t cfirst, int32_t own, Ctr& ct) {
-    FlatLds<K, !NUV>& L = flat_lds<K, !NUV>();
+    FlatLds<K, F::UV>& L = flat_lds<K, F::UV>();
     const uint32_t cc = uint32_t(__popc(cm));
     constexpr bool kInPlace = SELF;
 #ifndef ATR_INPLACE_FACTOR
@@ -306,11 +333,11 @@ __device__ __forceinline__ void cand_rounds(const Ray& r, const DModel& m, int w
             unsigned long long mine = kKeyInit;
             bool imp = false;
             float u = 0.f, v = 0.f;
-            if (valid) imp = cand_test<COUNT, K, !NUV>(q, m, w, own, slot, mine, u, v, ct);
+            if (valid) imp = cand_test<F, COUNT, K>(q, m, w, own, slot, mine, u, v, ct);
             __builtin_amdgcn_wave_barrier();
             if (imp && L.key[w][own] == mine) {  // this iteration's winner for its owner
                 L.slot[w][own] = slot;
-                if constexpr (!NUV) {
+                if constexpr (F::UV) {
                     L.u[w][own] = u;
                     L.v[w][own] = v;
                 }
@@ -345,7 +372,7 @@ __device__ __forceinline__ void cand_rounds(const Ray& r, const DModel& m, int w
         const uint32_t slot = uint32_t(__shfl(int(cfirst), s2)) + b;
         const int32_t ow = __shfl(own, s2);
         Ray q;
-        q.o = UO ? r.o : mk(shfl_f(r.o.x, ow), shfl_f(r.o.y, ow), shfl_f(r.o.z, ow));
+        q.o = F::UO ? r.o : mk(shfl_f(r.o.x, ow), shfl_f(r.o.y, ow), shfl_f(r.o.z, ow));
         q.d = mk(shfl_f(r.d.x, ow), shfl_f(r.d.y, ow), shfl_f(r.d.z, ow));
         unsigned long long mine = kKeyInit;
         bool imp = false;
@@ -367,7 +394,7 @@ __device__ __forceinline__ void cand_rounds(const Ray& r, const DModel& m, int w
         __builtin_amdgcn_wave_barrier();
         if (imp && L.key[w][ow] == mine) {  // this sub-round's winner for its owner
             L.slot[w][ow] = slot;
-            if constexpr (!NUV) {
+            if constexpr (F::UV) {
                 L.u[w][ow] = u;
                 L.v[w][ow] = v;
             }
@@ -376,11 +403,11 @@ __device__ __forceinline__ void cand_rounds(const Ray& r, const DModel& m, int w
     }
 }
 
-// The pieces of a clustered tree query (tree_closest_flat below; the path engine's bounce kernel
-// runs them in its own loop). Per lane: `done` (no query, or the query finished), `need` (a DFS pass
-// is due: the first, or a re-walk after a full buffer), j / nb / more (the current leaf of the
-// buffer, its fill, whether the pass found more than fits), `rewalk` (the buffer's last entry is the
-// next pass's bound). The result stays in the lane's LDS key/slot/u/v row (flat_result).
+// The pieces of a clustered tree query (flat_query below runs them). Per lane: `done` (no query, or
+// the query finished), `need` (a DFS pass is due: the first, or a re-walk after a full buffer), j /
+// nb / more (the current leaf of the buffer, its fill, whether the pass found more than fits),
+// `rewalk` (the buffer's last entry is the next pass's bound). The result stays in the lane's LDS
+// key/slot/u/v row (flat_result).
 
 // Start a query: the root box (kd_tree.cpp:339), the root leaf alone (:344-361) or a first pass.
 struct FlatQ {
@@ -388,16 +415,16 @@ struct FlatQ {
     bool done, need, more, rewalk;
 };
 
-// SEED (an occlusion query, occlusion.hip): the lane's key starts at `start` = bits(t_max) << 32
+// F::SEED (an occlusion query, occlusion.hip): the lane's key starts at `start` = bits(t_max) << 32
 // instead of kKeyInit, here and at every leaf step: the scan's exclusion bound is t_max from the
 // first cluster on, a candidate with t == t_max never compares below it (low word 0), and "this leaf
 // improved" is key != start. Without SEED `start` is not read.
-template <bool COUNT, int K = kLeafBuf, bool UV = true, bool SEED = false>
+template <class F, bool COUNT, int K = kLeafBuf>
 __device__ __forceinline__ FlatQ flat_begin(const Ray& r, const DModel& m, bool active, int w, int ln, Ctr& ct,
                                             unsigned long long start = kKeyInit) {
-    FlatLds<K, UV>& L = flat_lds<K, UV>();
+    FlatLds<K, F::UV>& L = flat_lds<K, F::UV>();
     FlatQ q{0, 0, true, false, false, false};
-    if constexpr (SEED) L.key[w][ln] = start;
+    if constexpr (F::SEED) L.key[w][ln] = start;
     else L.key[w][ln] = kKeyInit;
     if (active) {
         const NodeBox root = load_node(m.nodes, 0);
@@ -417,11 +444,11 @@ __device__ __forceinline__ FlatQ flat_begin(const Ray& r, const DModel& m, bool 
 }
 
 // One DFS pass (kd_tree.cpp:363-435) for every lane with `need`; its sorted leaves wait in LDS.
-// UT: the wave walks its passes together (traverse_pass_wave: coherent rays). LDSB: the pass inserts
-// straight into the LDS columns. NEAR (with LDSB): near-first passes (traverse_pass_near).
-template <bool COUNT, bool LDSB, bool UT, bool NEAR, int K = kLeafBuf, bool UV = true>
+// F::UT: the wave walks its passes together (traverse_pass_wave: coherent rays). F::LDSB: the pass
+// inserts straight into the LDS columns. F::NEAR (with LDSB): near-first passes (traverse_pass_near).
+template <class F, bool COUNT, int K = kLeafBuf>
 __device__ __forceinline__ void flat_pass(const Ray& r, const DModel& m, int w, int ln, FlatQ& q, int& err, Ctr& ct) {
-    FlatLds<K, UV>& L = flat_lds<K, UV>();
+    FlatLds<K, F::UV>& L = flat_lds<K, F::UV>();
     // the re-walk bound: the last leaf of the previous pass's full buffer (entry K - 1 of the column)
     const float bd = q.rewalk ? L.lbd[w][K - 1][ln] : -__builtin_inff();
     const int32_t bi = q.rewalk ? L.lbl[w][K - 1][ln] : -1;
@@ -431,7 +458,7 @@ __device__ __forceinline__ void flat_pass(const Ray& r, const DModel& m, int w, 
         if (n < 0) { err = 1; q.done = true; }
         else { q.nb = n < K ? n : K; q.more = n > K; if (q.nb == 0) q.done = true; }
     };
-    if constexpr (UT) {
+    if constexpr (F::UT) {
         if (__ballot(q.need)) {
             LdsLeafBuf<K> lb;
             lb.d = &L.lbd[w][0][ln];
@@ -441,11 +468,11 @@ __device__ __forceinline__ void flat_pass(const Ray& r, const DModel& m, int w, 
         }
     } else if (q.need) {
         int32_t n;
-        if constexpr (LDSB) {
+        if constexpr (F::LDSB) {
             LdsLeafBuf<K> lb;
             lb.d = &L.lbd[w][0][ln];
             lb.leaf = &L.lbl[w][0][ln];
-            if (NEAR && m.near_ok) n = traverse_pass_near<K, COUNT>(r, m.inner, lb, bd, bi, ct);
+            if (F::NEAR && m.near_ok) n = traverse_pass_near<K, COUNT>(r, m.inner, lb, bd, bi, ct);
             else n = traverse_pass<K, COUNT>(r, m.inner, lb, bd, bi, ct);
         } else {  // register buffer: the LDS one measured 5% slower for incoherent bounce rays
             LeafBuf<K> lb;
@@ -458,16 +485,16 @@ __device__ __forceinline__ void flat_pass(const Ray& r, const DModel& m, int w, 
 }
 
 // One leaf step of every lane with `live` (a query under way whose buffer is current): the
-// clusters of each such lane's current leaf, scanned lane-private or dealt over the wave (HYB
+// clusters of each such lane's current leaf, scanned lane-private or dealt over the wave (F::HYB
 // decides per step, wave-uniformly: deal when the largest cluster count exceeds hyb_a x rounds +
 // hyb_b; without HYB every step deals), candidates compacted. A leaf's result does not depend on
 // the visiting order (minimum (t, leaf rank)), so the choice changes no output bit. Then each live
 // lane stops at the first leaf that improved its hit (kd_tree.cpp:457-460), moves to its next
-// leaf, or asks for a re-walk. UO: one origin for the whole wave. NUV: u and v feed no output.
-// PADS: the box growths of each cluster come from `pads`, the camera's row of the per-camera table
+// leaf, or asks for a re-walk.
+// F::PADS: the box growths of each cluster come from `pads`, the camera's row of the per-camera table
 // at this model's first cluster (cluster.h cluster_grow; primary flavour only, wave-uniform).
 //
-// WCULL (the one-origin primary flavours; hv: the wave's direction hull, hull_pack): before the
+// F::WCULL (the one-origin primary flavours; hv: the wave's direction hull, hull_pack): before the
 // scan, the clusters of each distinct leaf of the step are tested once per wave against the hull
 // (cluster_hull_keep), lanes as clusters, two leaves at a time in the wave's halves; a ballot is the
 // leaf's survivor mask `sv`, kept by every lane that holds the leaf. The scan then visits the
@@ -475,17 +502,16 @@ __device__ __forceinline__ void flat_pass(const Ray& r, const DModel& m, int w, 
 // sequence of bounds, and with it every output and counter of a lane-private step, is what it was
 // (DESIGN.md §4b). Leaves of more than 32 clusters keep them all (sv all ones: survivor j is
 // cluster j).
-// SEED, start: as in flat_begin.
-template <bool COUNT, bool HYB, bool UO, bool NUV, int K = kLeafBuf, bool PADS = false, bool WCULL = false,
-          bool SEED = false>
+// F::SEED, start: as in flat_begin.
+template <class F, bool COUNT, int K = kLeafBuf>
 __device__ __forceinline__ void flat_leaf_step(const Ray& r, const DModel& m, int w, int ln, bool live, FlatQ& q,
                                                Ctr& ct, int32_t hyb_a, int32_t hyb_b, const float2_t* pads = nullptr,
                                                float hv = 0.f, unsigned long long start = kKeyInit) {
-    static_assert(!PADS || UO, "the table holds one origin per camera");
-    static_assert(!WCULL || (UO && K >= 2), "the hull is of one origin's directions; sv's LDS slot");
-    FlatLds<K, !NUV>& L = flat_lds<K, !NUV>();
-    // flavour of the scan (primary-only, camera, bounce rays) -> early screen normals (cluster.h)
-    constexpr bool kEarly = ((PADS ? 8 : NUV ? 1 : UO ? 2 : 4) & ATR_EARLY_NRM) != 0;
+    static_assert(!F::PADS || F::UO, "the table holds one origin per camera");
+    static_assert(!F::WCULL || (F::UO && K >= 2), "the hull is of one origin's directions; sv's LDS slot");
+    constexpr bool UO = F::UO, PADS = F::PADS, WCULL = F::WCULL;
+    FlatLds<K, F::UV>& L = flat_lds<K, F::UV>();
+    constexpr bool kEarly = (F::EARLY & ATR_EARLY_NRM) != 0;  // early screen normals (cluster.h)
     ATR_PCLK(const uint64_t tc2 = clock64());
     uint32_t cf = 0, cn = 0;
     if (live) {
@@ -538,10 +564,10 @@ __device__ __forceinline__ void flat_leaf_step(const Ray& r, const DModel& m, in
     const uint32_t incl = wave_incl_add(cn);  // inclusive prefix sum over the lanes
     const uint32_t excl = incl - cn;
     const uint32_t total = uint32_t(__builtin_amdgcn_readlane(int(incl), 63));
-    if constexpr (SEED) { if (live) L.key[w][ln] = start; }
+    if constexpr (F::SEED) { if (live) L.key[w][ln] = start; }
     else { if (live) L.key[w][ln] = kKeyInit; }
     bool deal = true;
-    if constexpr (HYB) {
+    if constexpr (F::HYB) {
         // the largest cluster count of the step (counts are small: the signed max is exact)
         const uint32_t mx = uint32_t(__builtin_amdgcn_readlane(wave_incl_max(int32_t(cn)), 63));
         deal = int32_t(mx) > hyb_a * int32_t((total + 63u) >> 6) + hyb_b;
@@ -567,7 +593,7 @@ __device__ __forceinline__ void flat_leaf_step(const Ray& r, const DModel& m, in
                 cm = cluster_cands<COUNT, kEarly, PADS>(r, m, c, m.clus[kClusterBlock * size_t(c)],
                                                 m.clus[kClusterBlock * size_t(c) + 1], bound, ct, pads);
             }
-            cand_rounds<COUNT, UO, NUV, true, K>(r, m, w, ln, cm, kMaxClusterSize * (cf + ci), ln, ct);
+            cand_rounds<F, COUNT, true, K>(r, m, w, ln, cm, kMaxClusterSize * (cf + ci), ln, ct);
         }
     }
     ATR_PCLK(if (!deal) ct.t_lp += uint32_t(clock64() - tc1));
@@ -604,12 +630,12 @@ __device__ __forceinline__ void flat_leaf_step(const Ray& r, const DModel& m, in
             cm = cluster_cands<COUNT, kEarly, PADS>(qr, m, c, m.clus[kClusterBlock * size_t(c)],
                                                     m.clus[kClusterBlock * size_t(c) + 1], bound, ct, pads);
         }
-        cand_rounds<COUNT, UO, NUV, false, K>(r, m, w, ln, cm, kMaxClusterSize * c, own, ct);
+        cand_rounds<F, COUNT, false, K>(r, m, w, ln, cm, kMaxClusterSize * c, own, ct);
     }
     ATR_PCLK(if (deal) ct.t_deal += uint32_t(clock64() - tc1));
     if (live) {  // stop at the first leaf that improved the hit (kd_tree.cpp:457-460)
         bool improved;
-        if constexpr (SEED) improved = L.key[w][ln] != start;
+        if constexpr (F::SEED) improved = L.key[w][ln] != start;
         else improved = L.key[w][ln] != kKeyInit;
         if (improved) {
             q.done = true;
@@ -622,16 +648,16 @@ __device__ __forceinline__ void flat_leaf_step(const Ray& r, const DModel& m, in
 }
 
 // The lane's result from its LDS row (t = kMaxFloat: no hit).
-template <bool NUV, int K = kLeafBuf>
+template <class F, bool COUNT, int K = kLeafBuf>
 __device__ __forceinline__ void flat_result(const DModel& m, bool active, int w, int ln, Hit& h) {
-    FlatLds<K, !NUV>& L = flat_lds<K, !NUV>();
+    FlatLds<K, F::UV>& L = flat_lds<K, F::UV>();
     h.t = kMaxFloat;
     h.face = 0;
     h.u = h.v = 0.f;
     const unsigned long long key = L.key[w][ln];
     if (active && key != kKeyInit) {
         h.t = __uint_as_float(uint32_t(key >> 32));
-        if constexpr (!NUV) {
+        if constexpr (F::UV) {
             h.u = L.u[w][ln];
             h.v = L.v[w][ln];
         }
@@ -640,43 +666,31 @@ __device__ __forceinline__ void flat_result(const DModel& m, bool active, int w,
 }
 
 // One tree query of every active lane of the wave (called by all 64 lanes, converged): passes and
-// leaf steps until every lane's query is done. Flags as above.
-template <bool COUNT, bool HYB = false, bool LDSB = false, bool UO = false, bool UT = false, bool NUV = false,
-          bool NEAR = false, int K = kLeafBuf, bool PADS = false, bool WCULL = false>
-__device__ __forceinline__ void tree_closest_flat(const Ray& r, const DModel& m, bool active, Hit& h, int& err,
-                                                  Ctr& ct, int32_t hyb_a = 0, int32_t hyb_b = 0,
-                                                  const float2_t* pads = nullptr, int32_t wcull = 0) {
-    const int w = threadIdx.x >> 6, ln = threadIdx.x & 63;
-    ATR_PCLK(uint64_t tcs = clock64());
-    FlatQ q = flat_begin<COUNT, K, !NUV>(r, m, active, w, ln, ct);
-    // WCULL: the direction hull of the lanes that passed the root box, once per query; switched off
+// leaf steps until every lane's query is done; the result stays in the lane's LDS row. start: the
+// key every lane starts from (F::SEED, flat_begin).
+template <class F, bool COUNT, int K = kLeafBuf>
+__device__ __forceinline__ void flat_query(const Ray& r, const DModel& m, bool active, int w, int ln, int& err, Ctr& ct,
+                                           int32_t hyb_a = 0, int32_t hyb_b = 0, const float2_t* pads = nullptr,
+                                           int32_t wcull = 0, unsigned long long start = kKeyInit) {
+    FlatQ q = flat_begin<F, COUNT, K>(r, m, active, w, ln, ct, start);
+    // F::WCULL: the direction hull of the lanes that passed the root box, once per query; switched off
     // (wcull == 0, wave-uniform) the hull is unusable and every leaf step keeps all its clusters
     // (the hull waits in one VGPR, hull_pack, instead of seven SGPRs held through the passes)
     [[maybe_unused]] float hv = __builtin_nanf("");
-    if constexpr (WCULL) {
+    if constexpr (F::WCULL) {
         if (wcull) hv = hull_pack(wave_hull(r, !q.done), ln);
     }
     for (;;) {
-        ATR_PCLK(const uint64_t tc0 = clock64());
-        flat_pass<COUNT, LDSB, UT, NEAR, K, !NUV>(r, m, w, ln, q, err, ct);
-        ATR_PCLK(ct.t_pass += uint32_t(clock64() - tc0));
+        ATR_PCLK(uint64_t tc0 = 0; if constexpr (!F::SEED) tc0 = clock64());  // no clocks in an occlusion query
+        flat_pass<F, COUNT, K>(r, m, w, ln, q, err, ct);
+        ATR_PCLK(if constexpr (!F::SEED) ct.t_pass += uint32_t(clock64() - tc0));
         if (__ballot(!q.done) == 0) break;
-        flat_leaf_step<COUNT, HYB, UO, NUV, K, PADS, WCULL>(r, m, w, ln, !q.done, q, ct, hyb_a, hyb_b, pads, hv);
+        flat_leaf_step<F, COUNT, K>(r, m, w, ln, !q.done, q, ct, hyb_a, hyb_b, pads, hv, start);
     }
-    flat_result<NUV, K>(m, active, w, ln, h);
-    ATR_PCLK(ct.t_scan += uint32_t(clock64() - tcs));
 }
 
 // ------------------------------------------------------------------ get_intersection_data
 enum { SCHED_LANE = 0, SCHED_FLAT = 6, SCHED_HYBRID = 7 };
-// Flavours of the clustered scan: CAMERA rays (one origin, coherent: HYBRID's wave-walked passes,
-// LDS leaf buffer), BOUNCE rays (incoherent: dealt rounds, register leaf buffer), PRIMARY-only
-// frames (CAMERA without u and v); PRIMARY_PADS: PRIMARY with the clusters' box growths read from
-// the per-camera table (cluster.h cluster_grow).
-enum { FLAV_CAMERA = 0, FLAV_BOUNCE = 1, FLAV_PRIMARY = 2, FLAV_HYB_BOUNCE = 3, FLAV_PRIMARY_PADS = 4 };
-#ifndef ATR_BOUNCE_HYB  // experiment builds: 1 = the path engine's bounce rays choose lane-private or
-#define ATR_BOUNCE_HYB 0  // dealt leaf steps per step as HYBRID does (thresholds hybrid_a, hybrid_b)
-#endif
 
 // A model's table pointers as wave-uniform GLOBAL pointers (uniform_global, trace.h): read once per
 // query into SGPRs and cast to the global address space (through the DScene reference the compiler
@@ -707,11 +721,11 @@ struct SceneHit {
 
 // get_intersection_data (renderer.cpp:34-160) for every lane of the wave (converged call; inactive
 // lanes take part in the wave-wide scans). SCHED_LANE: per-lane reference scan; otherwise the
-// clustered scan in flavour FLAV. intersect_models is the models' part; scene_finish (shade.h) the
+// clustered scan in flavour F. intersect_models is the models' part; scene_finish (shade.h) the
 // spheres, planes and hit record, so a caller can re-read o and d between the two instead of
-// holding them through the query. pads (FLAV_PRIMARY_PADS): the camera's row of the table of box
+// holding them through the query. pads (FlavPrimaryPads): the camera's row of the table of box
 // growths, one pair per cluster of the scene (model i's from cl_base on); wave-uniform.
-template <int SCHED, int FLAV, bool COUNT, int KB = kLeafBuf>
+template <int SCHED, class F, bool COUNT, int KB = kLeafBuf>
 __device__ __forceinline__ SceneHit intersect_models(const DScene* __restrict__ S, V3 o, V3 d, bool active, int& err,
                                                     Ctr& ct, int32_t hyb_a, int32_t hyb_b,
                                                     const float2_t* pads = nullptr, int32_t wcull = 0) {
@@ -725,19 +739,15 @@ __device__ __forceinline__ SceneHit intersect_models(const DScene* __restrict__ 
             if constexpr (SCHED == SCHED_LANE) {
                 if (active) tree_closest_lane<COUNT>(r, m, h, err, ct);
                 else h.t = kMaxFloat;
-            } else if constexpr (FLAV == FLAV_CAMERA)
-                tree_closest_flat<COUNT, true, true, true, true, false>(r, m, active, h, err, ct, hyb_a, hyb_b);
-            else if constexpr (FLAV == FLAV_PRIMARY)
-                tree_closest_flat<COUNT, true, true, true, true, true, false, kLeafBuf, false, true>(
-                    r, m, active, h, err, ct, hyb_a, hyb_b, nullptr, wcull);
-            else if constexpr (FLAV == FLAV_PRIMARY_PADS)
-                tree_closest_flat<COUNT, true, true, true, true, true, false, kLeafBuf, true, true>(
-                    r, m, active, h, err, ct, hyb_a, hyb_b, pads + __builtin_amdgcn_readfirstlane(m.cl_base), wcull);
-            else if constexpr (FLAV == FLAV_HYB_BOUNCE)
-                tree_closest_flat<COUNT, true, false, false, false, false>(r, m, active, h, err, ct, hyb_a, hyb_b);
-            else  // bounce rays: near-first passes into the LDS leaf buffer, every step dealt
-                tree_closest_flat<COUNT, ATR_BOUNCE_HYB != 0, true, false, false, false, true, KB>(r, m, active, h, err, ct,
-                                                                                         hyb_a, hyb_b);
+            } else {
+                const float2_t* mp = pads;  // the row's entries of this model
+                if constexpr (F::PADS) mp = pads + __builtin_amdgcn_readfirstlane(m.cl_base);
+                const int w = threadIdx.x >> 6, ln = threadIdx.x & 63;
+                ATR_PCLK(uint64_t tcs = clock64());
+                flat_query<F, COUNT, KB>(r, m, active, w, ln, err, ct, hyb_a, hyb_b, mp, wcull);
+                flat_result<F, COUNT, KB>(m, active, w, ln, h);
+                ATR_PCLK(ct.t_scan += uint32_t(clock64() - tcs));
+            }
             if (h.t > kTol && h.t < sh.best) { sh.best = h.t; sh.face = h.face; sh.fu = h.u; sh.fv = h.v; sh.nm = i; }
         } else if (active) {  // brute force (:58-82), face-ordered triangles, uniform loads
             if constexpr (COUNT) { ct.box += 1; ct.box_all += 1; }
@@ -756,11 +766,11 @@ __device__ __forceinline__ SceneHit intersect_models(const DScene* __restrict__ 
     return sh;
 }
 
-template <int SCHED, int FLAV, bool COUNT>
+template <int SCHED, class F, bool COUNT>
 __device__ __forceinline__ void intersect_scene(const DScene* __restrict__ S, V3 o, V3 d, bool active, Isect& id,
                                                 int& err, Ctr& ct, int32_t hyb_a, int32_t hyb_b,
                                                 const float2_t* pads = nullptr, int32_t wcull = 0) {
-    const SceneHit sh = intersect_models<SCHED, FLAV, COUNT>(S, o, d, active, err, ct, hyb_a, hyb_b, pads, wcull);
+    const SceneHit sh = intersect_models<SCHED, F, COUNT>(S, o, d, active, err, ct, hyb_a, hyb_b, pads, wcull);
     if (!active) return;
     scene_finish(S, o, d, sh.best, sh.face, sh.fu, sh.fv, sh.nm, id);  // :86-160
 }

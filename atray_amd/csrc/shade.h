@@ -15,35 +15,43 @@ struct Isect {
     uint32_t face;
 };
 
+// The t of a ray's hit with a sphere (sphere.h:12-39) or a plane (plane.h:12-22); 0: no hit.
+__device__ __forceinline__ float sphere_t(V3 o, V3 d, const DSphere& sp) {
+    const V3 pc = sub(o, mk(sp.cx, sp.cy, sp.cz));
+    const float pcs = len2(pc);
+    const float b = 2 * (dot(d, pc));
+    const float bs = b * b;
+    const float c = pcs - sp.r * sp.r;
+    const float dmt = bs - (4 * c);
+    float t = 0;
+    if (!(dmt < 0)) {
+        const float ta = (-b + sqrtf(dmt)) * 0.5f;
+        const float tb = (-b - sqrtf(dmt)) * 0.5f;
+        if (ta <= 0 && tb <= 0) t = 0;
+        else if (tb > 0) t = tb;
+        else t = ta;
+    }
+    return t;
+}
+__device__ __forceinline__ float plane_t(V3 o, V3 d, const DPlane& pl) {
+    const V3 n = mk(pl.nx, pl.ny, pl.nz);
+    const float denom = dot(n, d);
+    float t = 0;
+    if (!(denom > -kTol && denom < kTol)) t = (pl.d - dot(o, n)) / denom;
+    return t;
+}
+
 // best/face/fu/fv/nm: the closest model hit so far (nm = -1: none).
 __device__ __forceinline__ void scene_finish(const DScene* __restrict__ S, V3 o, V3 d, float best, uint32_t face,
                                              float fu, float fv, int32_t nm, Isect& id) {
     int32_t ns = -1, np = -1;
     const int32_t nspheres = __builtin_amdgcn_readfirstlane(S->nspheres), nplanes = __builtin_amdgcn_readfirstlane(S->nplanes);
-    for (int32_t i = 0; i < nspheres; ++i) {  // sphere.h:12-39
-        const DSphere& sp = uniform_global(S->spheres)[i];
-        const V3 pc = sub(o, mk(sp.cx, sp.cy, sp.cz));
-        const float pcs = len2(pc);
-        const float b = 2 * (dot(d, pc));
-        const float bs = b * b;
-        const float c = pcs - sp.r * sp.r;
-        const float dmt = bs - (4 * c);
-        float t = 0;
-        if (!(dmt < 0)) {
-            const float ta = (-b + sqrtf(dmt)) * 0.5f;
-            const float tb = (-b - sqrtf(dmt)) * 0.5f;
-            if (ta <= 0 && tb <= 0) t = 0;
-            else if (tb > 0) t = tb;
-            else t = ta;
-        }
+    for (int32_t i = 0; i < nspheres; ++i) {
+        const float t = sphere_t(o, d, uniform_global(S->spheres)[i]);
         if (t > kTol && t < best) { best = t; ns = i; }
     }
-    for (int32_t i = 0; i < nplanes; ++i) {  // plane.h:12-22
-        const DPlane& pl = uniform_global(S->planes)[i];
-        const V3 n = mk(pl.nx, pl.ny, pl.nz);
-        const float denom = dot(n, d);
-        float t = 0;
-        if (!(denom > -kTol && denom < kTol)) t = (pl.d - dot(o, n)) / denom;
+    for (int32_t i = 0; i < nplanes; ++i) {
+        const float t = plane_t(o, d, uniform_global(S->planes)[i]);
         if (t > kTol && t < best) { np = i; best = t; }
     }
     id.t = best;

@@ -1,5 +1,6 @@
 // sort_key.h -- the (direction cell, origin cell) key of a ray (PathSort, engine.h), shared by the
-// path engine's queue sort (paths.hip) and the ray queries' batch order (query.hip).
+// path engine's queue sort (paths.hip) and the ray queries' batch order (query.hip); load_ray, how
+// the ray and occlusion queries (query.hip, occlusion.hip) read a ray of the caller's batch.
 #pragma once
 #include "engine.h"
 
@@ -8,6 +9,13 @@
 #endif
 
 namespace atr {
+
+__device__ __forceinline__ void load_ray(const float* __restrict__ po, const float* __restrict__ pd, uint32_t e, V3& o,
+                                         V3& d) {
+    const size_t b = 3 * size_t(e);
+    o = mk(po[b], po[b + 1], po[b + 2]);
+    d = mk(pd[b], pd[b + 1], pd[b + 2]);
+}
 
 // Sort key of a queued ray (PathSort, engine.h): the octahedral cell of its direction (kSortDirs x
 // kSortDirs over the unfolded octahedron) and the Morton code of its origin's cell, b bits per axis
