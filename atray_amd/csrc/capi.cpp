@@ -1834,6 +1834,84 @@ int atr_occluded_rays(atr_ctx* c, const float* origins, const float* directions,
                       });
 }
 
+// A hemisphere gather (atray.h): the queries' claim counter, ring set and hand-over
+// between streams (query_call without an order), its own kernel; the per-point outputs are zeroed on
+// the stream first, inside the timed range.
+int atr_gather_occlusion(atr_ctx* c, const float* points, const float* normals, const float* t_max, int64_t npoints,
+                         int32_t nsamples, uint32_t first_sample, int64_t point_base, uint64_t seed,
+                         const atr_gather_out* out, int32_t variant, void* stream) {
+    if (!c) return ATR_E_INVALID;
+    if (npoints < 0 || nsamples < 1 || nsamples > 65536) return ATR_E_INVALID;
+    if (uint64_t(first_sample) + uint64_t(nsamples) > (uint64_t(1) << 24)) return ATR_E_INVALID;
+    if (point_base < 0 || npoints > (int64_t(1) << 39) || point_base > (int64_t(1) << 39) - npoints) return ATR_E_INVALID;
+    if (npoints >= (int64_t(1) << 31) || npoints * int64_t(nsamples) >= (int64_t(1) << 31)) return ATR_E_INVALID;
+    if (npoints > 0 && (!out || !points || !normals)) return ATR_E_INVALID;
+    if (variant != ATR_KERNEL_AUTO && variant != ATR_KERNEL_FLAT && variant != ATR_KERNEL_LANE) return ATR_E_INVALID;
+    if (!c->d_scene) return ATR_E_NOSCENE;
+    if (npoints == 0) return ATR_OK;
+    const uint32_t words = (uint32_t(nsamples) + 31u) / 32u;
+    return query_call(c, nullptr, nullptr, npoints * int64_t(nsamples), 0, stream, out->traced_rays,
+                      [&](QueryParams& Q, hipStream_t s) -> hipError_t {
+                          GatherParams P;
+                          std::memset(&P, 0, sizeof(P));
+                          P.scene = Q.scene;
+                          P.p = points;
+                          P.nrm = normals;
+                          P.tmax = t_max;
+                          P.n = Q.n;
+                          P.nsamples = uint32_t(nsamples);
+                          P.first_sample = first_sample;
+                          P.words = words;
+                          P.point_base = point_base;
+                          P.seed = seed;
+                          P.visible = out->visible;
+                          P.occluded = out->occluded;
+                          P.mask = out->mask;
+                          P.dirs = out->dirs;
+                          P.traced_rays = Q.traced_rays;
+                          P.error_flag = Q.error_flag;
+                          P.head = Q.head;
+                          hipError_t e = hipSuccess;
+                          const size_t per = size_t(npoints) * sizeof(uint32_t);
+                          if (P.visible && (e = hipMemsetAsync(P.visible, 0, per, s)) != hipSuccess) return e;
+                          if (P.occluded && (e = hipMemsetAsync(P.occluded, 0, per, s)) != hipSuccess) return e;
+                          if (P.mask && (e = hipMemsetAsync(P.mask, 0, per * words, s)) != hipSuccess) return e;
+                          return atr_launch_gather(P, variant == ATR_KERNEL_LANE ? 1 : 0, c->ncu, s);
+                      });
+}
+
+// The gather's sampler on the host (atray.h): the kernel's own functions (engine.h), compiled with the
+// library's -ffp-contract=off. No device, no context.
+int atr_gather_directions(const float* normals, int64_t npoints, int32_t nsamples, uint32_t first_sample,
+                          int64_t point_base, uint64_t seed, float* dirs_out, uint8_t* traced_out) {
+    if (npoints < 0 || nsamples < 1 || nsamples > 65536) return ATR_E_INVALID;
+    if (uint64_t(first_sample) + uint64_t(nsamples) > (uint64_t(1) << 24)) return ATR_E_INVALID;
+    if (point_base < 0 || npoints > (int64_t(1) << 39) || point_base > (int64_t(1) << 39) - npoints) return ATR_E_INVALID;
+    if (npoints >= (int64_t(1) << 31) || npoints * int64_t(nsamples) >= (int64_t(1) << 31)) return ATR_E_INVALID;
+    if (npoints > 0 && !normals) return ATR_E_INVALID;
+    const V3 zero = mk(0.f, 0.f, 0.f);
+    for (int64_t i = 0; i < npoints; ++i) {
+        const V3 n = mk(normals[3 * i], normals[3 * i + 1], normals[3 * i + 2]);
+        const bool nok = ray_ok(zero, n);  // the direction test on the normal
+        for (int32_t s = 0; s < nsamples; ++s) {
+            const int64_t k = i * nsamples + s;
+            V3 d = zero;
+            bool traced = false;
+            if (nok) {
+                d = gather_dir(seed, point_base + i, first_sample + uint32_t(s), n);
+                traced = ray_ok(zero, d) && dot(d, n) > 0.0f;
+            }
+            if (dirs_out) {
+                dirs_out[3 * k] = d.x;
+                dirs_out[3 * k + 1] = d.y;
+                dirs_out[3 * k + 2] = d.z;
+            }
+            if (traced_out) traced_out[k] = traced ? 1 : 0;
+        }
+    }
+    return ATR_OK;
+}
+
 int atr_render_adaptive_info(atr_ctx* c, int64_t info_out[4]) {
     if (!c || !info_out || c->adapt_last < 0) return ATR_E_INVALID;
     HIPCHK(hipSetDevice(c->device));

@@ -372,6 +372,42 @@ struct OcclParams {
     const uint32_t* perm;  // sorted launches: position -> ray
 };
 
+// A hemisphere gather (atr_gather_occlusion, gather.hip): npoints surface points with
+// unit normals, nsamples directions each, drawn in the kernel (gather_dir below); item i * nsamples + s
+// of the flattened batch is sample first_sample + s of point point_base + i. Persistent waves claim
+// 64 items at a time on `head`. visible, occluded and mask (words per point) are zeroed before the
+// launch and added / ORed to; a null output is not written.
+struct GatherParams {
+    const DScene* scene;
+    const float* p;        // 3 per point
+    const float* nrm;      // 3 per point
+    const float* tmax;     // one per point, or null
+    uint32_t n;            // npoints x nsamples (< 2^31)
+    uint32_t nsamples;
+    uint32_t first_sample;
+    uint32_t words;        // mask words per point: ceil(nsamples / 32)
+    int64_t point_base;
+    uint64_t seed;
+    uint32_t* visible;
+    uint32_t* occluded;
+    uint32_t* mask;
+    float* dirs;           // 3 per item
+    unsigned long long* traced_rays;  // 64 spread counters (a ring slot), or null
+    int32_t* error_flag;
+    uint32_t* head;        // zeroed before the launch
+};
+
+// Sample `sample` of point `point` around the unit normal n: bounce_shade's diffuse direction (scan.h)
+// on the (pixel, sample) stream of path_stream. A zero sum gives NaN, which ray_ok rejects.
+ATR_HD V3 gather_dir(uint64_t seed, int64_t point, uint32_t sample, V3 n) {
+    uint64_t st, stream;
+    path_stream(seed, point, sample, st, stream);
+    const float r0 = rand_bi(st, stream);
+    const float r1 = rand_bi(st, stream);
+    const float r2 = rand_bi(st, stream);
+    return unit(add(mk(r0, r1, r2), n));
+}
+
 // The validity test of a caller's ray (atray.h atr_trace_rays): six finite inputs and a direction
 // normalised to within 2^-20 in len2 (what unit() leaves is within 6 x 2^-24). The comparisons are
 // false for a NaN, and an infinite component fails the first one.
@@ -380,6 +416,15 @@ ATR_HD bool ray_ok(V3 o, V3 d) {
     const bool fin = fabsf(o.x) <= kMaxFloat && fabsf(o.y) <= kMaxFloat && fabsf(o.z) <= kMaxFloat &&
                      fabsf(d.x) <= kMaxFloat && fabsf(d.y) <= kMaxFloat && fabsf(d.z) <= kMaxFloat;
     return fin && fabsf(len2(d) - 1.0f) <= kRayLen2Tol;
+}
+
+// The validity test of a gather's point (atray.h atr_gather_occlusion): a finite point and a unit
+// normal (the ray test), and a t_max that is positive or +inf, tested on its bits (NaN, zero and
+// negative values fail, whatever the denormal mode).
+ATR_HD bool gather_point_ok(V3 p, V3 n, float tm) {
+    int32_t tb;
+    __builtin_memcpy(&tb, &tm, sizeof(tb));
+    return ray_ok(p, n) && tb > 0 && tb <= 0x7F800000;
 }
 
 }  // namespace atr

@@ -32,6 +32,8 @@ hipError_t atr_launch_sort_bins(const atr::PathSort& so, hipStream_t s);  // als
 hipError_t atr_launch_query_sort(const atr::QueryParams& P, int ncu, hipStream_t s);
 hipError_t atr_launch_query(const atr::QueryParams& P, int lane, int ncu, hipStream_t s);
 hipError_t atr_launch_occlusion(const atr::OcclParams& P, int lane, int ncu, hipStream_t s);
+// gather.hip
+hipError_t atr_launch_gather(const atr::GatherParams& P, int lane, int ncu, hipStream_t s);
 // plan.hip
 hipError_t atr_launch_plan(const atr::DBlock* base, int32_t nb, unsigned long long* cost,
                            unsigned long long* cost_last, void* work, atr::DBlock* out, int32_t max_split,

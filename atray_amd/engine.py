@@ -101,6 +101,11 @@ class atr_ray_hits(C.Structure):
                 ("traced_rays", C.c_void_p)]
 
 
+class atr_gather_out(C.Structure):
+    _fields_ = [("visible", C.c_void_p), ("occluded", C.c_void_p), ("mask", C.c_void_p), ("dirs", C.c_void_p),
+                ("traced_rays", C.c_void_p)]
+
+
 class atr_tuning(C.Structure):
     _fields_ = [("xcd_chunk", C.c_int32), ("frame_rotate", C.c_int32), ("hybrid_a", C.c_int32),
                 ("hybrid_b", C.c_int32), ("path_batch_log2", C.c_int32), ("cluster_size", C.c_int32),
@@ -127,7 +132,7 @@ EXPORTS = [
     "atr_unpack_masked_ranks",
     "atr_render_plan_info", "atr_workspace_info", "atr_render_start_samples",
     "atr_render_start_adaptive", "atr_render_adaptive_info", "atr_render_cull_counters",
-    "atr_trace_rays", "atr_occluded_rays",
+    "atr_trace_rays", "atr_occluded_rays", "atr_gather_occlusion", "atr_gather_directions",
 ]
 # the diagnostic build's extra symbols (include/atray_diag.h; make -C atray_amd/csrc DIAG=1)
 DIAG_EXPORTS = ["atr_render_wave_trace", "atr_render_phase_clocks", "atr_render_path_counters",
@@ -183,6 +188,9 @@ def lib():
         "atr_render_adaptive_info": ([vp, i64 * 4], C.c_int),
         "atr_trace_rays": ([vp, vp, vp, i64, P(atr_ray_hits), i32, i32, vp], C.c_int),
         "atr_occluded_rays": ([vp, vp, vp, vp, i64, vp, vp, i32, i32, vp], C.c_int),
+        "atr_gather_occlusion": ([vp, vp, vp, vp, i64, i32, u32, i64, C.c_uint64, P(atr_gather_out), i32, vp],
+                                 C.c_int),
+        "atr_gather_directions": ([vp, i64, i32, u32, i64, C.c_uint64, vp, vp], C.c_int),
         "atr_render_packed_size": ([vp, i32], i64),
         "atr_render_counters": ([vp, P(atr_camera), vp, i32, C.c_uint64, i32, i64 * 10], C.c_int),
         "atr_render_cull_counters": ([vp, P(atr_camera), vp, i32, C.c_uint64, i32, i64 * 5], C.c_int),
@@ -458,6 +466,43 @@ def segment_rays(p, q, margin=1e-3):
     return p, v * inv[:, None], length * keep
 
 
+def gather_directions(normals, nsamples, first_sample=0, point_base=0, seed=0):
+    """atr_gather_directions: the gather's sampler on the host, no device. normals: (n, 3) float32
+    (numpy, or anything numpy converts). Returns (dirs (n, nsamples, 3) float32, traced (n, nsamples)
+    uint8): the direction of every (point, sample) and whether gather_occlusion traces it (above the
+    tangent plane and a valid direction); a normal that is not unit gives zeros."""
+    nrm = np.ascontiguousarray(normals, np.float32)
+    if nrm.ndim != 2 or nrm.shape[1] != 3:
+        raise ValueError("normals: an (n, 3) float32 array is required")
+    n, ns = len(nrm), int(nsamples)
+    dirs = np.zeros((n, max(ns, 0), 3), np.float32)
+    traced = np.zeros((n, max(ns, 0)), np.uint8)
+    check(lib().atr_gather_directions(nrm.ctypes.data if n else None, n, ns, int(first_sample), int(point_base),
+                                      C.c_uint64(int(seed) & (2**64 - 1)), dirs.ctypes.data if dirs.size else None,
+                                      traced.ctypes.data if traced.size else None), "gather directions")
+    return dirs, traced
+
+
+def surface_points(orig, dirs, t, normal):
+    """A trace_rays result as a gather's input, in bounce_shade's convention: (p, n) with p = o + d * t
+    (a multiply, then an add, each rounded on its own) and n = the hit's normal, negated where
+    dot(-d, n) < 0 (dot as engine.h: (x*x' + y*y') + z*z'). Pure torch: (n, 3) float32 tensors and an
+    (n,) float32 t, on any one device. Rows of rays that missed are the caller's to drop."""
+    import torch
+    for name, a in (("orig", orig), ("dirs", dirs), ("normal", normal)):
+        if not isinstance(a, torch.Tensor) or a.dtype != torch.float32 or a.dim() != 2 or a.shape[1] != 3:
+            raise ValueError(f"{name}: an (n, 3) float32 tensor is required")
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 1:
+        raise ValueError("t: an (n,) float32 tensor is required")
+    if not (orig.shape == dirs.shape == normal.shape and t.shape[0] == orig.shape[0]):
+        raise ValueError("orig, dirs, t and normal differ in length")
+    p = orig + dirs * t[:, None]
+    m = -dirs
+    att = (m[:, 0] * normal[:, 0] + m[:, 1] * normal[:, 1]) + m[:, 2] * normal[:, 2]
+    n = torch.where((att < 0)[:, None], -normal, normal)
+    return p, n
+
+
 class Engine:
     """One device context (atr_ctx): scene upload + renders on a HIP stream."""
 
@@ -618,6 +663,71 @@ class Engine:
         orig, dirs, t_max = segment_rays(p, q, margin)
         return self.occluded_rays(orig.contiguous(), dirs.contiguous(), t_max.contiguous(), variant=variant,
                                   sort_bits=sort_bits, stream=stream)
+
+    # atr_gather_out outputs: name -> elements per point or per (point, sample)
+    _GATHER_OUTPUTS = ("visible", "occluded", "mask", "dirs")
+
+    def gather_occlusion(self, points, normals, nsamples, t_max=None, first_sample=0, point_base=0, seed=0,
+                         variant=ATR_KERNEL_AUTO, stream=None, outputs=("visible", "occluded")):
+        """atr_gather_occlusion: nsamples hemisphere directions per surface point, drawn on the device and
+        answered as occluded_rays answers them. points, normals: contiguous (n, 3) float32 tensors on the
+        engine's device (unit normals); t_max: a contiguous (n,) float32 tensor there, or None (unbounded).
+        Returns ({name: tensor} for the requested outputs -- visible, occluded: (n,) int32 counts; mask:
+        (n, ceil(nsamples / 32)) int32 words, bit s % 32 of word s // 32 set iff sample s is visible;
+        dirs: (n, nsamples, 3) float32 -- and the traced-sample count as a one-element int64 tensor);
+        valid once the stream has run, e.g. after wait()."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        for name, a in (("points", points), ("normals", normals)):
+            if not isinstance(a, torch.Tensor) or a.dtype != torch.float32 or a.dim() != 2 or a.shape[1] != 3:
+                raise ValueError(f"{name}: an (n, 3) float32 tensor is required")
+            if a.device != dev:
+                raise ValueError(f"{name}: not on {dev}")
+            if not a.is_contiguous():
+                raise ValueError(f"{name}: not contiguous")
+        if points.shape[0] != normals.shape[0]:
+            raise ValueError("points and normals differ in length")
+        n, ns = int(points.shape[0]), int(nsamples)
+        if t_max is not None:
+            if not isinstance(t_max, torch.Tensor) or t_max.dtype != torch.float32 or t_max.dim() != 1:
+                raise ValueError("t_max: an (n,) float32 tensor is required")
+            if t_max.device != dev:
+                raise ValueError(f"t_max: not on {dev}")
+            if not t_max.is_contiguous():
+                raise ValueError("t_max: not contiguous")
+            if t_max.shape[0] != n:
+                raise ValueError("t_max and points differ in length")
+        bad = [k for k in outputs if k not in self._GATHER_OUTPUTS]
+        if bad:
+            raise ValueError(f"unknown outputs {bad}")
+        if not 1 <= ns <= 65536:
+            raise ValueError("nsamples: 1..65536")
+        shapes = {"visible": ((n,), torch.int32), "occluded": ((n,), torch.int32),
+                  "mask": ((n, (ns + 31) // 32), torch.int32), "dirs": ((n, ns, 3), torch.float32)}
+        out = {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device=dev) for k in outputs}
+        traced = torch.zeros(1, dtype=torch.int64, device=dev)
+        go = atr_gather_out(*[out[k].data_ptr() if k in out and n else None for k in self._GATHER_OUTPUTS],
+                            traced.data_ptr())
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        check(lib().atr_gather_occlusion(self.h, C.c_void_p(points.data_ptr()) if n else None,
+                                         C.c_void_p(normals.data_ptr()) if n else None,
+                                         C.c_void_p(t_max.data_ptr()) if n and t_max is not None else None, n, ns,
+                                         int(first_sample), int(point_base), C.c_uint64(int(seed) & (2**64 - 1)),
+                                         C.byref(go), int(variant), C.c_void_p(stream) if stream else None),
+              "gather occlusion")
+        return out, traced
+
+    def ambient_occlusion(self, points, normals, nsamples, t_max=None, first_sample=0, point_base=0, seed=0,
+                          variant=ATR_KERNEL_AUTO, stream=None):
+        """The visible share of every point's traced samples, visible / max(visible + occluded, 1), as an
+        (n,) float32 tensor (gather_occlusion's arguments; computed on torch's current stream, so pass
+        that stream or None)."""
+        import torch
+        out, _ = self.gather_occlusion(points, normals, nsamples, t_max, first_sample, point_base, seed, variant,
+                                       stream, outputs=("visible", "occluded"))
+        vis, occ = out["visible"], out["occluded"]
+        return vis.to(torch.float32) / torch.clamp(vis + occ, min=1).to(torch.float32)
 
     def adaptive_info(self):
         """The last adaptive pass's counts, once wait() returned 0: (pixels live at its start, blocks

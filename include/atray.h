@@ -26,7 +26,8 @@ extern "C" {
 /* ABI 2 (round 6): atr_tuning gained reserved[4] (zero; room for later knobs without a size
    change); ABI 1's last two words became path_sort_bits and path_split in round 5.
    atr_trace_rays and atr_ray_hits were added since without a version change: no existing struct
-   or entry point changed. atr_occluded_rays likewise. */
+   or entry point changed. atr_occluded_rays likewise; atr_gather_occlusion, atr_gather_out and
+   atr_gather_directions likewise. */
 #define ATR_ABI_VERSION 2
 
 enum {
@@ -537,6 +538,64 @@ enum { ATR_OCCL_VISIBLE = 0, ATR_OCCL_OCCLUDED = 1, ATR_OCCL_INVALID = 2 };
 int atr_occluded_rays(atr_ctx* ctx, const float* origins, const float* directions, const float* t_max,
                       int64_t nrays, uint8_t* occluded, unsigned long long* traced_rays,
                       int32_t variant, int32_t sort_bits, void* stream);
+
+/* Hemisphere gathers (ambient occlusion, sky visibility, the visibility term of a lightmap or vertex
+   baker): for npoints surface points with unit normals, nsamples directions per point are drawn on
+   the device and each one is answered as atr_occluded_rays answers it; per point the counts and a
+   bit per sample come back. No ray array exists anywhere.
+   Samples. Sample s of point i is the renderer's own diffuse direction (cast_ray's random direction
+   for a surface with scatter 0) on the renderer's per-(pixel, sample) PCG stream, in separately
+   rounded f32 operations in this order:
+     state, stream = the path stream of (seed, pixel = point_base + i, sample = first_sample + s):
+                     state = splitmix64(seed ^ pixel ^ sample << 40), increment 2 pixel + 1;
+     r0, r1, r2    = three rand_bi draws (-1 + 2 * (float(pcg32) * 2.328306437e-10f)), in that order;
+     d             = v * (1 / sqrtf(len2(v))) with v = (r0, r1, r2) + n.
+   Which samples are traced. A sample is traced iff (p, d) passes atr_trace_rays' validity test (this
+   covers the NaN of a zero sum) and dot(d, n) = (d.x*n.x + d.y*n.y) + d.z*n.z > 0. The sampler reaches
+   below the tangent plane for oblique normals (0 % of the draws for an axis normal, 3 to 4 % for
+   others), where the culled triangle test would call an inward ray visible. A sample that is not
+   traced counts in neither visible nor occluded, has mask bit 0 and does not count in traced_rays.
+   What a traced sample answers: exactly atr_occluded_rays for (p, d, t_max[i]) -- the same window,
+   the same culled test, the same walk.
+   points, normals: DEVICE, 3 floats per point. t_max: DEVICE, one float per point, or NULL = unbounded;
+   atr_occluded_rays' rules (+inf counts as 3.402823466e38; NaN, zero or negative is invalid;
+   0 < t_max <= 1e-4 is valid and visible).
+   Invalid points. A point is invalid when p is not finite, n fails the direction test
+   (fabsf(len2(n) - 1.0f) <= 0x1p-20f) or its t_max is bad. Both its counts are 0, its mask words 0,
+   its dirs 0,0,0; nothing is traced and its neighbours are untouched.
+   Ranges, ATR_E_INVALID otherwise: nsamples 1..65,536; first_sample + nsamples <= 2^24;
+   point_base >= 0 and point_base + npoints <= 2^39; npoints >= 0 and npoints * nsamples < 2^31.
+   Split invariance (from the streams; part of the contract): a batch cut in two calls at any point,
+   the second with point_base advanced by the cut, gives the per-point outputs of one call; a sample
+   range cut in two calls, the second with first_sample advanced by the cut, gives counts that add up
+   and masks that concatenate.
+   Each call WRITES its outputs: visible, occluded and mask are zeroed on the stream by the call and
+   then accumulated; nothing is added to what was there (traced_rays alone is an accumulator).
+   variant: ATR_KERNEL_AUTO and ATR_KERNEL_FLAT = the clustered scan, ATR_KERNEL_LANE = the per-lane
+   reference scan; the same outputs; any other value is ATR_E_INVALID. There is no sort_bits: the
+   batch is coherent by origin as it comes. Asynchronous on `stream`; atr_render_wait covers it
+   (tiles_done 0; a tree-depth flag surfaces as ATR_E_TREE_DEPTH), atr_last_kernel_ms times it.
+   npoints == 0: ATR_OK, nothing is enqueued or written. ATR_E_INVALID also for ctx NULL and for out,
+   points or normals NULL with npoints > 0. ATR_E_NOSCENE before an upload. No struct and no ABI version
+   change. */
+typedef struct {            /* DEVICE pointers; any may be NULL */
+    uint32_t* visible;      /* per point: traced samples with no hit in (1e-4, t_max) */
+    uint32_t* occluded;     /* per point: traced samples with one */
+    uint32_t* mask;         /* per point ceil(nsamples/32) words; bit s%32 of word s/32 set iff sample s is visible */
+    float*    dirs;         /* 3 floats per (point, sample), point-major: the generated direction */
+    unsigned long long* traced_rays;   /* one accumulator, += traced samples */
+} atr_gather_out;
+int atr_gather_occlusion(atr_ctx* ctx, const float* points, const float* normals, const float* t_max,
+                         int64_t npoints, int32_t nsamples, uint32_t first_sample, int64_t point_base,
+                         uint64_t seed, const atr_gather_out* out, int32_t variant, void* stream);
+/* Host only, no device: the same sampler, for a caller that weights the mask bits by direction.
+   normals: HOST, 3 floats per point. dirs_out (3 floats per (point, sample), point-major) and
+   traced_out (one byte per (point, sample): 1 iff the direction passes the validity test and lies
+   above the tangent plane) are HOST and optional. A normal that fails the direction test gives
+   0,0,0 and 0 for its samples. The same range checks; ATR_E_INVALID for normals NULL with
+   npoints > 0. */
+int atr_gather_directions(const float* normals, int64_t npoints, int32_t nsamples, uint32_t first_sample,
+                          int64_t point_base, uint64_t seed, float* dirs_out, uint8_t* traced_out);
 
 /* wait_for_render_from_camera_to_finish: 1 = still running after timeout_ms, 0 = done,
    <0 = error. tiles_done (optional) = tiles of the last render known complete (progress). */
