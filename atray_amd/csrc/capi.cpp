@@ -368,6 +368,26 @@ hipError_t wait_all(atr_ctx* c) {
     return e;
 }
 
+// A launch's set of 64 spread traced-ray counters from the ring: ring_take hands out the next set
+// (zeroed by the finish kernel of the launch that last used it, which s first waits for) and
+// ring_done, after the launch's own finish kernel (atr_launch_traced_finish), records the set's
+// event -- the launch's completion event.
+hipError_t ring_take(atr_ctx* c, hipStream_t s, int& k, unsigned long long*& slots) {
+    k = c->tnext;
+    c->tnext = (k + 1) % kQueueSlots;
+    if (c->tused[k]) {
+        const hipError_t e = hipStreamWaitEvent(s, c->tev[k], 0);
+        if (e != hipSuccess) return e;
+    }
+    slots = reinterpret_cast<unsigned long long*>(static_cast<char*>(c->tring) + size_t(k) * kTraceBytes);
+    return hipSuccess;
+}
+hipError_t ring_done(atr_ctx* c, hipStream_t s, int k) {
+    const hipError_t e = hipEventRecord(c->tev[k], s);
+    if (e == hipSuccess) c->tused[k] = true;
+    return e;
+}
+
 void free_scene(atr_ctx* c) {
     for (DevBuf& b : c->scene_bufs) (void)hipFree(b.p);
     c->scene_bufs.clear();
@@ -662,6 +682,95 @@ hipError_t path_workspace(atr_ctx* c, hipStream_t s, int64_t cap, int64_t grow_t
     return hipSuccess;
 }
 
+// The queue sort's cells over the scene box (PathSort: bits, bins, lo, sc), for the path engine's
+// queues and the ray queries' batch order alike.
+int32_t clamp_sort_bits(int32_t bits) {
+    while (bits > 0 && (int64_t(kSortDirs) * kSortDirs << (3 * bits)) > kSortBinsMax) --bits;
+    return bits;
+}
+void sort_cells(const atr_ctx* c, int32_t bits, PathSort& so) {
+    so.bits = bits;
+    so.nbins = int32_t(kSortDirs * kSortDirs) << (3 * bits);
+    const float* box = c->scene_box;
+    for (int a = 0; a < 3; ++a) {
+        so.lo[a] = box[a];
+        const float ext = box[3 + a] - box[a];
+        so.sc[a] = ext > 0.0f ? float(1 << bits) / ext : 0.0f;
+    }
+}
+
+// The workspace of a path launch over `ncells` cells of per_cell paths each (a render's 8x8 cells, a
+// radiance query's groups of 64 rays) and the cells per batch it allows: a batch of
+// 2^path_batch_log2 paths, halved while the device cannot hold its workspace (down to 2^lg_min
+// paths; the outputs do not depend on the batch size); then the same without the queue sort
+// (sort_bits comes back 0).
+hipError_t path_batches(atr_ctx* c, hipStream_t s, int64_t per_cell, int64_t ncells, int32_t levels, int32_t lg_min,
+                        bool live, int32_t& sort_bits, atr_ctx::PathWS*& ws, int64_t& cells) {
+    hipError_t e = hipErrorOutOfMemory;
+    for (;;) {
+        const int64_t bins = sort_bits > 0 ? int64_t(kSortDirs) * kSortDirs << (3 * sort_bits) : 0;
+        for (int32_t lg = c->tune.path_batch_log2; lg >= lg_min && e == hipErrorOutOfMemory; --lg) {
+            const int64_t batch = std::max<int64_t>(1, (int64_t(1) << lg) / per_cell);
+            cells = std::min<int64_t>(batch, ncells);
+            // capacity: this launch's paths rounded up to 2^24 (at most a full batch): a one-frame c4
+            // launch holds its 132.7 M paths (21 GB), not a whole 2^28 batch; a workspace that has to
+            // grow grows to a full batch at once, so a stream regrows at most once (a regrow inside a
+            // timed multi-frame run once measured a 4x slower c4 line, round 6)
+            const int64_t need = cells * per_cell, gran = int64_t(1) << 24;
+            const int64_t cap = std::max(need, std::min((need + gran - 1) / gran * gran, batch * per_cell));
+            e = path_workspace(c, s, cap, std::max(batch * per_cell, cap), std::max(levels, 8), bins, live, ws);
+            if (e == hipSuccess && ws->cap < cap) e = hipErrorOutOfMemory;
+        }
+        if (e != hipErrorOutOfMemory || sort_bits == 0) break;
+        sort_bits = 0;
+    }
+    return e;
+}
+
+// A workspace's queues, result slots and control words and, with sort_bits > 0, its queue-sort
+// buffers, bound to a launch.
+void bind_path_workspace(const atr_ctx* c, const atr_ctx::PathWS* ws, int32_t sort_bits, PathParams& Q) {
+    float4_t* base = static_cast<float4_t*>(ws->mem.p);
+    Q.cap = ws->cap;
+    Q.q[0] = base;
+    Q.q[1] = base + kPathPlanes * ws->cap;
+    Q.out = base + 2 * kPathPlanes * ws->cap;
+    Q.ctl = reinterpret_cast<PathCtl*>(base + (2 * kPathPlanes + 1) * ws->cap);
+    if (sort_bits > 0) {
+        PathSort& so = Q.sort;
+        sort_cells(c, sort_bits, so);
+        char* sb = static_cast<char*>(ws->mem.p) + sort_offset(ws->cap, ws->levels);
+        so.kr = reinterpret_cast<uint2_t*>(sb);
+        sb += size_t(ws->cap) * 8;
+        so.perm = reinterpret_cast<uint32_t*>(sb);
+        sb += size_t(ws->cap) * 4;
+        so.hist = reinterpret_cast<uint32_t*>(sb);
+        so.start = so.hist + ws->sort_bins;
+        so.part = so.start + ws->sort_bins;
+    }
+}
+
+// A batch's control words and sort bins zeroed, ahead of its entry launch.
+hipError_t reset_path_batch(const PathParams& Q, int32_t levels, int32_t sort_bits, hipStream_t s) {
+    const hipError_t e = hipMemsetAsync(Q.ctl, 0, sizeof(PathCtl) * size_t(levels), s);
+    if (e != hipSuccess || sort_bits <= 0) return e;
+    return hipMemsetAsync(Q.sort.hist, 0, sizeof(uint32_t) * size_t(Q.sort.nbins), s);
+}
+
+// Bounce levels 1 .. bl - 1 of a batch whose entry launch filled queue 0.
+hipError_t launch_bounce_levels(atr_ctx* c, PathParams& Q, int32_t bl, int32_t sort_bits, hipStream_t s) {
+    hipError_t e;
+    for (int32_t k = 1; k < bl; ++k) {
+        if (sort_bits > 0) {  // level k - 1's queue in key order (the launches zero the bins)
+            Q.bounce = k - 1;
+            if ((e = atr_launch_path_sort(Q, c->ncu, s)) != hipSuccess) return e;
+        }
+        Q.bounce = k;
+        if ((e = atr_launch_path_bounce(Q, c->ncu, c->tune.path_bounce_occ, s)) != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
 // The sample-parallel path engine (paths.hip) over a cell launch's blocks: the cell list in
 // batches of 2^tuning.path_batch_log2 paths, per batch the camera launch, one launch per further
 // bounce (persistent waves over the previous level's queue) and the per-pixel resolve, all on s.
@@ -676,34 +785,13 @@ hipError_t launch_paths_range(atr_ctx* c, const RenderParams& P, hipStream_t s, 
     const int64_t per_cell = 64 * std::max<int64_t>(spp, 1);
     const int32_t levels = std::max(bl, 1);
     // the queue sort pays off only when a level's queue feeds another bounce launch
-    int32_t sort_bits = bl >= 2 ? c->tune.path_sort_bits : 0;
-    while (sort_bits > 0 && (int64_t(kSortDirs) * kSortDirs << (3 * sort_bits)) > kSortBinsMax) --sort_bits;
+    int32_t sort_bits = clamp_sort_bits(bl >= 2 ? c->tune.path_sort_bits : 0);
     atr_ctx::PathWS* ws = nullptr;
-    hipError_t e = hipErrorOutOfMemory;
     int64_t cells = 0;
-    // a batch of 2^path_batch_log2 paths, halved while the device cannot hold its workspace (down to
-    // 2^16 paths; the outputs do not depend on the batch size); then the same without the queue sort
     // An adaptive pass has no cell-kernel fallback, so it tries the tuned batch size itself even
     // below 2^16 paths (other launches with such a tuning get no workspace here and render FLAT).
     const int32_t lg_min = live ? std::min(16, c->tune.path_batch_log2) : 16;
-    for (;;) {
-        const int64_t bins = sort_bits > 0 ? int64_t(kSortDirs) * kSortDirs << (3 * sort_bits) : 0;
-        for (int32_t lg = c->tune.path_batch_log2; lg >= lg_min && e == hipErrorOutOfMemory; --lg) {
-            const int64_t batch = std::max<int64_t>(1, (int64_t(1) << lg) / per_cell);
-            cells = std::min<int64_t>(batch, cend - cbeg);
-            // capacity: this launch's paths rounded up to 2^24 (at most a full batch): a one-frame c4
-            // launch holds its 132.7 M paths (21 GB), not a whole 2^28 batch; a workspace that has to
-            // grow grows to a full batch at once, so a stream regrows at most once (a regrow inside a
-            // timed multi-frame run once measured a 4x slower c4 line, round 6)
-            const int64_t need = cells * per_cell, gran = int64_t(1) << 24;
-            const int64_t cap = std::max(need, std::min((need + gran - 1) / gran * gran, batch * per_cell));
-            e = path_workspace(c, s, cap, std::max(batch * per_cell, cap), std::max(levels, 8), bins, live != nullptr,
-                               ws);
-            if (e == hipSuccess && ws->cap < cap) e = hipErrorOutOfMemory;
-        }
-        if (e != hipErrorOutOfMemory || sort_bits == 0) break;
-        sort_bits = 0;
-    }
+    hipError_t e = path_batches(c, s, per_cell, cend - cbeg, levels, lg_min, live != nullptr, sort_bits, ws, cells);
     if (e != hipSuccess) return e;
     PathParams Q;
     std::memset(&Q, 0, sizeof(Q));
@@ -724,12 +812,7 @@ hipError_t launch_paths_range(atr_ctx* c, const RenderParams& P, hipStream_t s, 
     Q.error_flag = P.error_flag;
     Q.block_cost = P.block_cost;
     Q.counters = P.counters;
-    float4_t* base = static_cast<float4_t*>(ws->mem.p);
-    Q.cap = ws->cap;
-    Q.q[0] = base;
-    Q.q[1] = base + kPathPlanes * ws->cap;
-    Q.out = base + 2 * kPathPlanes * ws->cap;
-    Q.ctl = reinterpret_cast<PathCtl*>(base + (2 * kPathPlanes + 1) * ws->cap);
+    bind_path_workspace(c, ws, sort_bits, Q);
     Q.xcd_chunk = P.xcd_chunk;
     Q.hyb_a = P.hyb_a;
     Q.hyb_b = P.hyb_b;
@@ -747,46 +830,17 @@ hipError_t launch_paths_range(atr_ctx* c, const RenderParams& P, hipStream_t s, 
         Q.live.part = Q.live.group + cells;
         Q.live.ctl = reinterpret_cast<PathLiveCtl*>(lb + live_bytes(ws->cap) - 256);
     }
-    if (sort_bits > 0) {
-        PathSort& so = Q.sort;
-        so.bits = sort_bits;
-        so.nbins = int32_t(kSortDirs * kSortDirs) << (3 * sort_bits);
-        const float* box = c->scene_box;
-        for (int a = 0; a < 3; ++a) {
-            so.lo[a] = box[a];
-            const float ext = box[3 + a] - box[a];
-            so.sc[a] = ext > 0.0f ? float(1 << sort_bits) / ext : 0.0f;
-        }
-        char* sb = static_cast<char*>(ws->mem.p) + sort_offset(ws->cap, ws->levels);
-        so.kr = reinterpret_cast<uint2_t*>(sb);
-        sb += size_t(ws->cap) * 8;
-        so.perm = reinterpret_cast<uint32_t*>(sb);
-        sb += size_t(ws->cap) * 4;
-        so.hist = reinterpret_cast<uint32_t*>(sb);
-        so.start = so.hist + ws->sort_bins;
-        so.part = so.start + ws->sort_bins;
-    }
-    const int occ_cam = c->tune.path_camera_occ, occ_bounce = c->tune.path_bounce_occ;
+    const int occ_cam = c->tune.path_camera_occ;
     for (int64_t c0 = cbeg; c0 < cend; c0 += cells) {
         Q.cell0 = int32_t(c0);
         Q.ncells = int32_t(std::min<int64_t>(cells, cend - c0));
         if (live && (e = atr_launch_path_live(Q, s)) != hipSuccess) return e;
         if (bl > 0 && spp > 0) {
-            if ((e = hipMemsetAsync(Q.ctl, 0, sizeof(PathCtl) * size_t(levels), s)) != hipSuccess) return e;
-            if (sort_bits > 0 &&
-                (e = hipMemsetAsync(Q.sort.hist, 0, sizeof(uint32_t) * size_t(Q.sort.nbins), s)) != hipSuccess)
-                return e;
+            if ((e = reset_path_batch(Q, levels, sort_bits, s)) != hipSuccess) return e;
             if ((e = live ? atr_launch_path_camera_adaptive(Q, c->ncu, s) : atr_launch_path_camera(Q, occ_cam, s)) !=
                 hipSuccess)
                 return e;
-            for (int32_t k = 1; k < bl; ++k) {
-                if (sort_bits > 0) {  // level k - 1's queue in key order (the launches zero the bins)
-                    Q.bounce = k - 1;
-                    if ((e = atr_launch_path_sort(Q, c->ncu, s)) != hipSuccess) return e;
-                }
-                Q.bounce = k;
-                if ((e = atr_launch_path_bounce(Q, c->ncu, occ_bounce, s)) != hipSuccess) return e;
-            }
+            if ((e = launch_bounce_levels(c, Q, bl, sort_bits, s)) != hipSuccess) return e;
         }
         if ((e = live ? atr_launch_path_resolve_adaptive(Q, s) : atr_launch_path_resolve(Q, s)) != hipSuccess) return e;
     }
@@ -933,18 +987,15 @@ hipError_t launch_render(atr_ctx* c, RenderParams& P, int sched, hipStream_t s, 
                          const PathLive* live) {
     if (done) *done = nullptr;
     if (!P.traced_rays) return launch_kernels(c, P, sched, s, live);
-    const int k = c->tnext;
-    c->tnext = (k + 1) % kQueueSlots;
-    hipError_t e;
-    if (c->tused[k] && (e = hipStreamWaitEvent(s, c->tev[k], 0)) != hipSuccess) return e;
+    int k = -1;
     unsigned long long* caller = P.traced_rays;
-    P.traced_rays = reinterpret_cast<unsigned long long*>(static_cast<char*>(c->tring) + size_t(k) * kTraceBytes);
+    hipError_t e = ring_take(c, s, k, P.traced_rays);
+    if (e != hipSuccess) return e;
     e = launch_kernels(c, P, sched, s, live);
     if (e == hipSuccess) e = atr_launch_traced_finish(P.traced_rays, caller, s);
     P.traced_rays = caller;
     if (e != hipSuccess) return e;
-    if ((e = hipEventRecord(c->tev[k], s)) != hipSuccess) return e;
-    c->tused[k] = true;
+    if ((e = ring_done(c, s, k)) != hipSuccess) return e;
     if (done) *done = c->tev[k];
     return hipSuccess;
 }
@@ -1712,8 +1763,7 @@ int query_call(atr_ctx* c, const float* origins, const float* directions, int64_
                void* stream, unsigned long long* traced_out, Launch launch) {
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    int32_t bits = sort_bits < 0 ? c->tune.path_sort_bits : sort_bits;
-    while (bits > 0 && (int64_t(kSortDirs) * kSortDirs << (3 * bits)) > kSortBinsMax) --bits;
+    const int32_t bits = clamp_sort_bits(sort_bits < 0 ? c->tune.path_sort_bits : sort_bits);
     const int64_t nbins = bits > 0 ? int64_t(kSortDirs) * kSortDirs << (3 * bits) : 0;
     atr_ctx::QueryWS& ws = c->query_ws;
     if (!ws.ev) HIPCHK(hipEventCreateWithFlags(&ws.ev, hipEventDisableTiming));
@@ -1746,14 +1796,7 @@ int query_call(atr_ctx* c, const float* origins, const float* directions, int64_
     Q.head = static_cast<uint32_t*>(ws.rays.p);
     if (bits > 0) {
         PathSort& so = Q.sort;
-        so.bits = bits;
-        so.nbins = int32_t(nbins);
-        const float* box = c->scene_box;  // the path engine's cells (launch_paths_range)
-        for (int a = 0; a < 3; ++a) {
-            so.lo[a] = box[a];
-            const float ext = box[3 + a] - box[a];
-            so.sc[a] = ext > 0.0f ? float(1 << bits) / ext : 0.0f;
-        }
+        sort_cells(c, bits, so);  // the path engine's cells
         char* rb = static_cast<char*>(ws.rays.p) + 256;
         so.kr = reinterpret_cast<uint2_t*>(rb);
         so.perm = reinterpret_cast<uint32_t*>(rb + size_t(ws.cap) * 8);
@@ -1767,19 +1810,13 @@ int query_call(atr_ctx* c, const float* origins, const float* directions, int64_
     ws.stream = s;
     hipEvent_t done = nullptr;
     int k = -1;
-    if (traced_out) {  // a zeroed set of 64 spread counters from the ring (launch_render)
-        k = c->tnext;
-        c->tnext = (k + 1) % kQueueSlots;
-        if (c->tused[k]) HIPCHK(hipStreamWaitEvent(s, c->tev[k], 0));
-        Q.traced_rays = reinterpret_cast<unsigned long long*>(static_cast<char*>(c->tring) + size_t(k) * kTraceBytes);
-    }
+    if (traced_out) HIPCHK(ring_take(c, s, k, Q.traced_rays));  // a zeroed set of 64 spread counters
     HIPCHK(hipMemsetAsync(Q.head, 0, sizeof(uint32_t), s));
     if (bits > 0) HIPCHK(atr_launch_query_sort(Q, c->ncu, s));
     HIPCHK(launch(Q, s));
     if (k >= 0) {
         HIPCHK(atr_launch_traced_finish(Q.traced_rays, traced_out, s));
-        HIPCHK(hipEventRecord(c->tev[k], s));
-        c->tused[k] = true;
+        HIPCHK(ring_done(c, s, k));
         done = c->tev[k];
     }
     HIPCHK(hipEventRecord(ws.ev, s));
@@ -1909,6 +1946,102 @@ int atr_gather_directions(const float* normals, int64_t npoints, int32_t nsample
             if (traced_out) traced_out[k] = traced ? 1 : 0;
         }
     }
+    return ATR_OK;
+}
+
+// Path-traced radiance along the caller's rays (atray.h): the path engine on a path
+// workspace, batched over groups of 64 rays the way launch_paths_range batches over cells, with the
+// entry kernel and the per-ray resolve of radiance.hip around the engine's own bounce levels. The
+// workspace is obtained before anything is enqueued and there is no cell-kernel fallback: the tuned
+// batch size is tried even below 2^16 paths, as for an adaptive pass. The traced rays go through a
+// set of the ring, as a render's and a query's do.
+int atr_radiance_rays(atr_ctx* c, const float* origins, const float* directions, int64_t nrays, int32_t nsamples,
+                      uint32_t first_sample, int64_t ray_base, int32_t bounce_limit, uint64_t seed,
+                      const atr_radiance_out* out, int32_t sort_bits, void* stream) {
+    if (!c) return ATR_E_INVALID;
+    if (nrays < 0 || nrays >= (int64_t(1) << 31) || nsamples < 1 || nsamples > 65536) return ATR_E_INVALID;
+    // the stream hash shifts the sample index by 40 bits, and float(total) is exact up to 2^24
+    if (uint64_t(first_sample) + uint64_t(nsamples) > (uint64_t(1) << 24)) return ATR_E_INVALID;
+    // the queues carry the stream index in 32 bits
+    if (ray_base < 0 || ray_base > (int64_t(1) << 32) - nrays) return ATR_E_INVALID;
+    if (bounce_limit < 1 || bounce_limit > kMaxPathBounces) return ATR_E_INVALID;
+    if (sort_bits != -1 && sort_bits != 0 && (sort_bits < 2 || sort_bits > kMaxSortBits)) return ATR_E_INVALID;
+    if (nrays > 0 && (!out || !origins || !directions)) return ATR_E_INVALID;
+    if (out && first_sample > 0 && !out->sum) return ATR_E_INVALID;
+    if (nrays > 0 && !out->rgb && !out->sum && !out->ray_casts && !out->invalid && !out->traced_rays)
+        return ATR_E_INVALID;
+    if (!c->d_scene) return ATR_E_NOSCENE;
+    if (nrays == 0) return ATR_OK;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int64_t per_group = 64 * int64_t(nsamples), groups = (nrays + 63) / 64;
+    // the order is of the bounce levels' queues: without a second level there is nothing to order
+    int32_t bits = clamp_sort_bits(bounce_limit >= 2 ? (sort_bits < 0 ? c->tune.path_sort_bits : sort_bits) : 0);
+    atr_ctx::PathWS* ws = nullptr;
+    int64_t cells = 0;
+    HIPCHK(path_batches(c, s, per_group, groups, bounce_limit, std::min(16, c->tune.path_batch_log2), false, bits, ws,
+                        cells));
+    PathParams Q;
+    std::memset(&Q, 0, sizeof(Q));
+    Q.cam.bounce_limit = bounce_limit;
+    Q.cam.samples_per_pixel = uint32_t(nsamples);
+    Q.scene = c->d_scene;
+    Q.seed = seed;
+    Q.error_flag = c->d_error;
+    Q.hyb_a = c->tune.hybrid_a;
+    Q.hyb_b = c->tune.hybrid_b;
+    bind_path_workspace(c, ws, bits, Q);
+    RadianceParams R;
+    std::memset(&R, 0, sizeof(R));
+    R.scene = Q.scene;
+    R.o = origins;
+    R.d = directions;
+    R.nsamples = uint32_t(nsamples);
+    R.first_sample = first_sample;
+    R.bounce_limit = bounce_limit;
+    R.hyb_a = Q.hyb_a;
+    R.hyb_b = Q.hyb_b;
+    R.ray_base = ray_base;
+    R.seed = seed;
+    R.q0 = Q.q[0];
+    R.cap = Q.cap;
+    R.out = Q.out;
+    R.ctl = Q.ctl;
+    R.sort = Q.sort;
+    R.error_flag = Q.error_flag;
+    R.rgb = out->rgb;
+    R.sum = out->sum;
+    R.ray_casts = out->ray_casts;
+    R.invalid = out->invalid;
+    c->prog_active = false;
+    HIPCHK(hipEventRecord(c->ev_start, s));
+    hipEvent_t done = nullptr;
+    int k = -1;
+    if (out->traced_rays) {
+        HIPCHK(ring_take(c, s, k, Q.traced_rays));
+        R.traced_rays = Q.traced_rays;
+    }
+    for (int64_t g0 = 0; g0 < groups; g0 += cells) {  // no batch crosses a group
+        const int64_t r0 = g0 * 64;
+        Q.ncells = int32_t(std::min<int64_t>(cells, groups - g0));
+        R.ray0 = uint32_t(r0);
+        R.n = uint32_t(std::min<int64_t>(int64_t(Q.ncells) * 64, nrays - r0));
+        HIPCHK(reset_path_batch(Q, bounce_limit, bits, s));
+        HIPCHK(atr_launch_radiance_entry(R, c->ncu, s));
+        HIPCHK(launch_bounce_levels(c, Q, bounce_limit, bits, s));
+        HIPCHK(atr_launch_radiance_resolve(R, s));
+    }
+    if (k >= 0) {
+        HIPCHK(atr_launch_traced_finish(Q.traced_rays, out->traced_rays, s));
+        HIPCHK(ring_done(c, s, k));
+        done = c->tev[k];
+    }
+    HIPCHK(hipEventRecord(ws->ev, s));
+    HIPCHK(record_stop(c, s, done));
+    HIPCHK(note_launch(c, s, c->ev_last != c->ev_stop));  // a ring event covers it
+    c->have_render = true;
+    c->last_stream = s;
+    c->last_ntiles = 0;
     return ATR_OK;
 }
 

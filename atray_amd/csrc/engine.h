@@ -397,6 +397,38 @@ struct GatherParams {
     uint32_t* head;        // zeroed before the launch
 };
 
+// A radiance query (atr_radiance_rays, radiance.hip): one batch of the call's rays,
+// [ray0, ray0 + n) of the arrays o and d, ray0 a multiple of 64. A group is 64 consecutive rays (the
+// path engine's "cell"); the entry kernel's persistent waves claim groups on ctl[0].head (zeroed with
+// the batch's control words; the bounce launches use the heads of levels >= 1 only), trace each
+// first segment once and seed queue 0 with the samples that go on; sample s of the batch's ray i has
+// the result slot (i / 64) x 64 nsamples + s x 64 + i % 64 and the stream of (seed, ray_base + ray0
+// + i, first_sample + s). The bounce levels are the path engine's own launches on a PathParams; the
+// resolve reads the slots and writes the outputs at the rays' input indices (a null one is not written).
+constexpr uint32_t kRayInvalid = 0xFFFFFFFEu;  // sample 0's slot of a ray that failed the validity test
+struct RadianceParams {
+    const DScene* scene;
+    const float* o;
+    const float* d;
+    uint32_t ray0, n;
+    uint32_t nsamples, first_sample;
+    int32_t bounce_limit;
+    int32_t hyb_a, hyb_b;
+    int64_t ray_base;
+    uint64_t seed;
+    float4_t* q0;     // queue 0 of the workspace (PathParams::q[0])
+    int64_t cap;
+    float4_t* out;    // the result slots (PathParams::out)
+    PathCtl* ctl;
+    PathSort sort;
+    unsigned long long* traced_rays;  // 64 spread counters (a ring slot), or null
+    int32_t* error_flag;
+    float* rgb;
+    float* sum;
+    uint32_t* ray_casts;
+    uint8_t* invalid;
+};
+
 // Sample `sample` of point `point` around the unit normal n: bounce_shade's diffuse direction (scan.h)
 // on the (pixel, sample) stream of path_stream. A zero sum gives NaN, which ray_ok rejects.
 ATR_HD V3 gather_dir(uint64_t seed, int64_t point, uint32_t sample, V3 n) {

@@ -34,6 +34,9 @@ hipError_t atr_launch_query(const atr::QueryParams& P, int lane, int ncu, hipStr
 hipError_t atr_launch_occlusion(const atr::OcclParams& P, int lane, int ncu, hipStream_t s);
 // gather.hip
 hipError_t atr_launch_gather(const atr::GatherParams& P, int lane, int ncu, hipStream_t s);
+// radiance.hip
+hipError_t atr_launch_radiance_entry(const atr::RadianceParams& P, int ncu, hipStream_t s);
+hipError_t atr_launch_radiance_resolve(const atr::RadianceParams& P, hipStream_t s);
 // plan.hip
 hipError_t atr_launch_plan(const atr::DBlock* base, int32_t nb, unsigned long long* cost,
                            unsigned long long* cost_last, void* work, atr::DBlock* out, int32_t max_split,

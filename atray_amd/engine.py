@@ -106,6 +106,11 @@ class atr_gather_out(C.Structure):
                 ("traced_rays", C.c_void_p)]
 
 
+class atr_radiance_out(C.Structure):
+    _fields_ = [("rgb", C.c_void_p), ("sum", C.c_void_p), ("ray_casts", C.c_void_p), ("invalid", C.c_void_p),
+                ("traced_rays", C.c_void_p)]
+
+
 class atr_tuning(C.Structure):
     _fields_ = [("xcd_chunk", C.c_int32), ("frame_rotate", C.c_int32), ("hybrid_a", C.c_int32),
                 ("hybrid_b", C.c_int32), ("path_batch_log2", C.c_int32), ("cluster_size", C.c_int32),
@@ -133,6 +138,7 @@ EXPORTS = [
     "atr_render_plan_info", "atr_workspace_info", "atr_render_start_samples",
     "atr_render_start_adaptive", "atr_render_adaptive_info", "atr_render_cull_counters",
     "atr_trace_rays", "atr_occluded_rays", "atr_gather_occlusion", "atr_gather_directions",
+    "atr_radiance_rays",
 ]
 # the diagnostic build's extra symbols (include/atray_diag.h; make -C atray_amd/csrc DIAG=1)
 DIAG_EXPORTS = ["atr_render_wave_trace", "atr_render_phase_clocks", "atr_render_path_counters",
@@ -191,6 +197,8 @@ def lib():
         "atr_gather_occlusion": ([vp, vp, vp, vp, i64, i32, u32, i64, C.c_uint64, P(atr_gather_out), i32, vp],
                                  C.c_int),
         "atr_gather_directions": ([vp, i64, i32, u32, i64, C.c_uint64, vp, vp], C.c_int),
+        "atr_radiance_rays": ([vp, vp, vp, i64, i32, u32, i64, i32, C.c_uint64, P(atr_radiance_out), i32, vp],
+                              C.c_int),
         "atr_render_packed_size": ([vp, i32], i64),
         "atr_render_counters": ([vp, P(atr_camera), vp, i32, C.c_uint64, i32, i64 * 10], C.c_int),
         "atr_render_cull_counters": ([vp, P(atr_camera), vp, i32, C.c_uint64, i32, i64 * 5], C.c_int),
@@ -503,6 +511,28 @@ def surface_points(orig, dirs, t, normal):
     return p, n
 
 
+def camera_rays(cam):
+    """The primary rays of an atr_camera without anti-aliasing, in pixel order (row y, then x), as
+    atr_render_start_ex casts them: (orig, dirs), (width * height, 3) float32 numpy arrays. Host-side,
+    every step a separately rounded f32 operation in the kernels' order (film_x, film_y, the point on
+    the film, unit()), so radiance_rays on them with ray_base 0 equals the render bit for bit, and a
+    slice of them with ray_base = its first pixel re-renders that region."""
+    F = np.float32
+    W, H = int(cam.width), int(cam.height)
+    v = lambda a: np.array([a.x, a.y, a.z], F)  # noqa: E731
+    eye, fc, cx, cy = v(cam.eye), v(cam.frame_center), v(cam.camera_x), v(cam.camera_y)
+    fy = F(-1.0) + F(2.0) * (np.arange(H, dtype=F) / F(H))
+    fx = ((F(-1.0) + F(2.0) * (np.arange(W, dtype=F) / F(W))) * F(cam.h_fov)) * F(cam.aspect_ratio)
+    fx, fy = np.tile(fx, H), np.repeat(fy, W)
+    p = (fc[None, :] + cx[None, :] * fx[:, None]) + cy[None, :] * fy[:, None]
+    d = p - eye[None, :]
+    len2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+    # the correctly rounded f32 square root, through f64 (as segment_rays)
+    inv = F(1.0) / np.sqrt(len2.astype(np.float64)).astype(F)
+    dirs = np.ascontiguousarray(d * inv[:, None], F)
+    return np.ascontiguousarray(np.broadcast_to(eye, dirs.shape), F), dirs
+
+
 class Engine:
     """One device context (atr_ctx): scene upload + renders on a HIP stream."""
 
@@ -728,6 +758,65 @@ class Engine:
                                        stream, outputs=("visible", "occluded"))
         vis, occ = out["visible"], out["occluded"]
         return vis.to(torch.float32) / torch.clamp(vis + occ, min=1).to(torch.float32)
+
+    # atr_radiance_out outputs: name -> (torch dtype name, elements per ray)
+    _RADIANCE_OUTPUTS = {"rgb": ("float32", 3), "sum": ("float32", 3), "ray_casts": ("int32", 1),
+                         "invalid": ("uint8", 1)}
+
+    def radiance_rays(self, orig, dirs, nsamples, bounces, seed=0, first_sample=0, ray_base=0, sort_bits=-1,
+                      stream=None, want=("rgb", "ray_casts", "invalid"), sum=None, ray_casts=None):
+        """atr_radiance_rays: the path-traced colour along every ray of a batch, nsamples samples of at
+        most `bounces` bounces each on the streams of (seed, ray_base + i, first_sample + s). orig, dirs:
+        contiguous (n, 3) float32 tensors on the engine's device, directions normalised (a ray that is
+        not, or not finite, comes back with invalid 1, untraced). `want` names the outputs (rgb, sum,
+        ray_casts, invalid). A later sample range continues an earlier one through `sum` (an (n, 3)
+        float32 tensor of an earlier call, required when first_sample > 0 and updated in place) and,
+        optionally, `ray_casts` (an (n,) int32 tensor of an earlier call, likewise). Enqueued on `stream`
+        (a raw HIP stream), or torch's current one. Returns ({name: tensor}, the traced-ray count as a
+        one-element int64 tensor); valid once the stream has run, e.g. after wait()."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        for name, a in (("orig", orig), ("dirs", dirs)):
+            if not isinstance(a, torch.Tensor) or a.dtype != torch.float32 or a.dim() != 2 or a.shape[1] != 3:
+                raise ValueError(f"{name}: an (n, 3) float32 tensor is required")
+            if a.device != dev:
+                raise ValueError(f"{name}: not on {dev}")
+            if not a.is_contiguous():
+                raise ValueError(f"{name}: not contiguous")
+        if orig.shape[0] != dirs.shape[0]:
+            raise ValueError("orig and dirs differ in length")
+        bad = [k for k in want if k not in self._RADIANCE_OUTPUTS]
+        if bad:
+            raise ValueError(f"unknown outputs {bad}")
+        n = int(orig.shape[0])
+        given = {"sum": sum, "ray_casts": ray_casts}
+        for k, a in given.items():
+            if a is None:
+                continue
+            dt, per = self._RADIANCE_OUTPUTS[k]
+            if (not isinstance(a, torch.Tensor) or a.dtype != getattr(torch, dt) or a.device != dev
+                    or not a.is_contiguous() or tuple(a.shape) != ((n, per) if per > 1 else (n,))):
+                raise ValueError(f"{k}: a contiguous {dt} tensor of {n} rays on {dev} is required")
+        if int(first_sample) > 0 and sum is None:
+            raise ValueError("sum: required when first_sample > 0")
+        out = {}
+        for k in tuple(want) + tuple(k for k, a in given.items() if a is not None and k not in want):
+            dt, per = self._RADIANCE_OUTPUTS[k]
+            if given.get(k) is not None:
+                out[k] = given[k]
+            else:
+                out[k] = torch.empty((n, per) if per > 1 else (n,), dtype=getattr(torch, dt), device=dev)
+        traced = torch.zeros(1, dtype=torch.int64, device=dev)
+        ro = atr_radiance_out(*[out[k].data_ptr() if k in out and n else None
+                                for k in ("rgb", "sum", "ray_casts", "invalid")], traced.data_ptr())
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        check(lib().atr_radiance_rays(self.h, C.c_void_p(orig.data_ptr()) if n else None,
+                                      C.c_void_p(dirs.data_ptr()) if n else None, n, int(nsamples),
+                                      int(first_sample), int(ray_base), int(bounces),
+                                      C.c_uint64(int(seed) & (2**64 - 1)), C.byref(ro), int(sort_bits),
+                                      C.c_void_p(stream) if stream else None), "radiance rays")
+        return out, traced
 
     def adaptive_info(self):
         """The last adaptive pass's counts, once wait() returned 0: (pixels live at its start, blocks

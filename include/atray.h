@@ -27,7 +27,7 @@ extern "C" {
    change); ABI 1's last two words became path_sort_bits and path_split in round 5.
    atr_trace_rays and atr_ray_hits were added since without a version change: no existing struct
    or entry point changed. atr_occluded_rays likewise; atr_gather_occlusion, atr_gather_out and
-   atr_gather_directions likewise. */
+   atr_gather_directions likewise; atr_radiance_rays and atr_radiance_out likewise. */
 #define ATR_ABI_VERSION 2
 
 enum {
@@ -596,6 +596,61 @@ int atr_gather_occlusion(atr_ctx* ctx, const float* points, const float* normals
    npoints > 0. */
 int atr_gather_directions(const float* normals, int64_t npoints, int32_t nsamples, uint32_t first_sample,
                           int64_t point_base, uint64_t seed, float* dirs_out, uint8_t* traced_out);
+
+/* Radiance along the caller's rays (a light-probe or lightmap baker, the reflection or GI pass of a
+   rasteriser, a region-of-interest or foveated re-render, a camera that is not a pinhole): what colour
+   arrives along this ray, by the renderer's own shading loop (cast_ray, renderer.cpp:213-262) on the
+   renderer's own streams.
+   Sample. Sample s of ray i is cast_ray(o_i, d_i, bounce_limit) on the path stream of (seed,
+   pixel = ray_base + i, sample = first_sample + s) (state = splitmix64(seed ^ pixel ^ sample << 40),
+   increment 2 pixel + 1). No draw is made before the first intersection: the caller's ray is the
+   path's first segment, as in the renderer's branch without anti-aliasing (renderer.cpp:348-357).
+   Every f32 operation is separately rounded, in cast_ray's order.
+   Outputs. sum is the ray's sample colours added in sample order, starting from 0 when
+   first_sample == 0. When first_sample > 0, sum is required: it is read as the starting value and
+   written back, and ray_casts (if given) is read, added to and written back -- the semantics of
+   atr_render_start_samples. rgb = sum / float(first_sample + nsamples), not clamped.
+   Consequences (each is tested):
+     1. With origins/directions the primary rays of a camera without anti-aliasing in pixel order,
+        ray_base = 0, the same seed, nsamples = samples_per_pixel and the same bounce_limit, rgb and
+        ray_casts equal atr_render_start_ex's IMAGE rgb and ray_casts, bit for bit.
+     2. A batch cut at any ray, the second call's ray_base advanced by the cut, gives the per-ray
+        outputs of one call; a sample range cut in two calls that continue through sum gives the
+        bits of one call.
+     3. No output bit depends on sort_bits, on the tuning's path_batch_log2, or on the stream.
+   Invalid rays. The validity test is atr_trace_rays' (six finite inputs, fabsf(len2(d) - 1.0f) <=
+   0x1p-20f). An invalid ray is not traced. With first_sample == 0 its rgb and sum are written 0,0,0 and
+   its ray_casts 0; with first_sample > 0 its sum and ray_casts are left as they are (and its rgb is
+   not written). Its invalid byte is 1. Its neighbours are untouched; no NaN reaches the traversal.
+   traced_rays accumulates the rays actually traced: one per valid ray for the first segment, which is
+   traced once per ray and not once per sample (every sample of a ray shares it), plus one per bounce
+   ray. This differs from the renderer's count, which traces the camera ray once per sample.
+   sort_bits: -1 = the tuning's path_sort_bits, 0 = queue order, 2..7 as for the path engine. It orders
+   each bounce level's queue; the first segment is traced in input order. With bounce_limit < 2 it has
+   no effect.
+   Ranges, ATR_E_INVALID otherwise: nrays 0 .. 2^31 - 1; nsamples 1..65,536; first_sample + nsamples
+   <= 2^24; ray_base >= 0 and ray_base + nrays <= 2^32 (the queues carry the stream index in 32
+   bits); bounce_limit 1..64; sort_bits as above. ATR_E_INVALID also for ctx NULL; for out, origins or
+   directions NULL with nrays > 0; for sum NULL with first_sample > 0; for all five pointers of out
+   NULL with nrays > 0. ATR_E_NOSCENE before an upload. nrays == 0: ATR_OK, nothing is enqueued or
+   written.
+   origins, directions: DEVICE, 3 floats per ray. Asynchronous on `stream`; atr_render_wait covers it
+   (tiles_done 0; a tree-depth flag surfaces as ATR_E_TREE_DEPTH), atr_last_kernel_ms times it. It
+   runs on a path workspace (atr_workspace_info counts it), in batches of the tuning's
+   2^path_batch_log2 paths over groups of 64 rays. There is no cell-kernel fallback: as with an
+   adaptive pass the tuned batch size is tried even below 2^16 paths, and if no workspace can be had
+   the call returns -(1000 + hipErrorOutOfMemory) before anything is enqueued, every buffer untouched.
+   No struct and no ABI version change. */
+typedef struct {            /* DEVICE pointers; any may be NULL (sum: see above) */
+    float*    rgb;          /* 3 per ray: sum / float(first_sample + nsamples), not clamped */
+    float*    sum;          /* 3 per ray: the running f32 sum of the ray's sample colours, in sample order */
+    uint32_t* ray_casts;    /* per ray: cast_ray's bounce count (renderer.cpp:260) summed over its samples */
+    uint8_t*  invalid;      /* per ray: 1 iff the ray failed the validity test, else 0 */
+    unsigned long long* traced_rays;   /* one accumulator */
+} atr_radiance_out;
+int atr_radiance_rays(atr_ctx* ctx, const float* origins, const float* directions, int64_t nrays,
+                      int32_t nsamples, uint32_t first_sample, int64_t ray_base, int32_t bounce_limit,
+                      uint64_t seed, const atr_radiance_out* out, int32_t sort_bits, void* stream);
 
 /* wait_for_render_from_camera_to_finish: 1 = still running after timeout_ms, 0 = done,
    <0 = error. tiles_done (optional) = tiles of the last render known complete (progress). */
