@@ -2045,6 +2045,107 @@ int atr_radiance_rays(atr_ctx* c, const float* origins, const float* directions,
     return ATR_OK;
 }
 
+// Hemisphere radiance gathered on the device (atray.h): atr_radiance_rays' flow with the
+// point as the unit of batching -- a batch is a whole number of points (at least one, even when
+// nsamples exceeds the tuned batch size), so a point's samples never straddle two batches and the
+// resolve sums them in sample order in one launch. The entry kernel and the per-point resolve of
+// gather_radiance.hip around the engine's own bounce levels; the workspace is obtained before anything
+// is enqueued and there is no cell-kernel fallback.
+int atr_gather_radiance(atr_ctx* c, const float* points, const float* normals, int64_t npoints, int32_t nsamples,
+                        uint32_t first_sample, int64_t point_base, int32_t bounce_limit, uint64_t seed,
+                        const atr_gather_radiance_out* out, int32_t sort_bits, void* stream) {
+    if (!c) return ATR_E_INVALID;
+    if (npoints < 0 || npoints >= (int64_t(1) << 31) || nsamples < 1 || nsamples > 65536) return ATR_E_INVALID;
+    if (npoints * int64_t(nsamples) >= (int64_t(1) << 31)) return ATR_E_INVALID;
+    // the stream hash shifts the sample index by 40 bits, and float(samples) is exact up to 2^24
+    if (uint64_t(first_sample) + uint64_t(nsamples) > (uint64_t(1) << 24)) return ATR_E_INVALID;
+    // the queues carry the stream index in 32 bits
+    if (point_base < 0 || point_base > (int64_t(1) << 32) - npoints) return ATR_E_INVALID;
+    if (bounce_limit < 1 || bounce_limit > kMaxPathBounces) return ATR_E_INVALID;
+    if (sort_bits != -1 && sort_bits != 0 && (sort_bits < 2 || sort_bits > kMaxSortBits)) return ATR_E_INVALID;
+    if (npoints > 0 && (!out || !points || !normals)) return ATR_E_INVALID;
+    if (out && first_sample > 0 && (!out->sum || !out->samples)) return ATR_E_INVALID;
+    if (npoints > 0 && !out->rgb && !out->sum && !out->samples && !out->ray_casts && !out->invalid &&
+        !out->sample_rgb && !out->dirs && !out->traced_rays)
+        return ATR_E_INVALID;
+    if (!c->d_scene) return ATR_E_NOSCENE;
+    if (npoints == 0) return ATR_OK;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // the order is of the bounce levels' queues: without a second level there is nothing to order
+    int32_t bits = clamp_sort_bits(bounce_limit >= 2 ? (sort_bits < 0 ? c->tune.path_sort_bits : sort_bits) : 0);
+    atr_ctx::PathWS* ws = nullptr;
+    int64_t per_batch = 0;  // points
+    HIPCHK(path_batches(c, s, nsamples, npoints, bounce_limit, std::min(16, c->tune.path_batch_log2), false, bits, ws,
+                        per_batch));
+    PathParams Q;
+    std::memset(&Q, 0, sizeof(Q));
+    Q.cam.bounce_limit = bounce_limit;
+    Q.cam.samples_per_pixel = uint32_t(nsamples);
+    Q.scene = c->d_scene;
+    Q.seed = seed;
+    Q.error_flag = c->d_error;
+    Q.hyb_a = c->tune.hybrid_a;
+    Q.hyb_b = c->tune.hybrid_b;
+    bind_path_workspace(c, ws, bits, Q);
+    GatherRadianceParams R;
+    std::memset(&R, 0, sizeof(R));
+    R.scene = Q.scene;
+    R.p = points;
+    R.nrm = normals;
+    R.nsamples = uint32_t(nsamples);
+    R.first_sample = first_sample;
+    R.bounce_limit = bounce_limit;
+    R.hyb_a = Q.hyb_a;
+    R.hyb_b = Q.hyb_b;
+    R.point_base = point_base;
+    R.seed = seed;
+    R.q0 = Q.q[0];
+    R.cap = Q.cap;
+    R.out = Q.out;
+    R.ctl = Q.ctl;
+    R.sort = Q.sort;
+    R.error_flag = Q.error_flag;
+    R.rgb = out->rgb;
+    R.sum = out->sum;
+    R.samples = out->samples;
+    R.ray_casts = out->ray_casts;
+    R.invalid = out->invalid;
+    R.sample_rgb = out->sample_rgb;
+    R.dirs = out->dirs;
+    c->prog_active = false;
+    HIPCHK(hipEventRecord(c->ev_start, s));
+    hipEvent_t done = nullptr;
+    int k = -1;
+    if (out->traced_rays) {
+        HIPCHK(ring_take(c, s, k, Q.traced_rays));
+        R.traced_rays = Q.traced_rays;
+    }
+    for (int64_t p0 = 0; p0 < npoints; p0 += per_batch) {  // whole points
+        const int64_t np = std::min<int64_t>(per_batch, npoints - p0);
+        Q.ncells = int32_t(np);
+        R.point0 = uint32_t(p0);
+        R.npoints = uint32_t(np);
+        R.n = uint32_t(np * int64_t(nsamples));
+        HIPCHK(reset_path_batch(Q, bounce_limit, bits, s));
+        HIPCHK(atr_launch_gather_radiance_entry(R, c->ncu, s));
+        HIPCHK(launch_bounce_levels(c, Q, bounce_limit, bits, s));
+        HIPCHK(atr_launch_gather_radiance_resolve(R, s));
+    }
+    if (k >= 0) {
+        HIPCHK(atr_launch_traced_finish(Q.traced_rays, out->traced_rays, s));
+        HIPCHK(ring_done(c, s, k));
+        done = c->tev[k];
+    }
+    HIPCHK(hipEventRecord(ws->ev, s));
+    HIPCHK(record_stop(c, s, done));
+    HIPCHK(note_launch(c, s, c->ev_last != c->ev_stop));  // a ring event covers it
+    c->have_render = true;
+    c->last_stream = s;
+    c->last_ntiles = 0;
+    return ATR_OK;
+}
+
 int atr_render_adaptive_info(atr_ctx* c, int64_t info_out[4]) {
     if (!c || !info_out || c->adapt_last < 0) return ATR_E_INVALID;
     HIPCHK(hipSetDevice(c->device));

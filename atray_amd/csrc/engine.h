@@ -429,10 +429,60 @@ struct RadianceParams {
     uint8_t* invalid;
 };
 
+// A hemisphere radiance gather (atr_gather_radiance, gather_radiance.hip): one batch of
+// the call's points, [point0, point0 + npoints) of the arrays p and nrm, nsamples samples each. Item
+// i * nsamples + s of the flattened batch is sample first_sample + s of point point_base + point0 + i
+// and owns result slot i * nsamples + s: a point's samples are contiguous, so the resolve reads 64 of
+// them as one 1-KB row. The entry kernel's persistent waves claim 64 items at a time on ctl[0].head,
+// draw the direction on the item's stream (gather_dir_state below), trace it and either finish the
+// path in its slot or append it to queue 0 with the stream as the draws left it; the bounce levels
+// are the path engine's own launches on a PathParams. Every item's slot is written exactly once: a
+// finished path's {colour, casts}, kSampleUntraced for a sample of a valid point that is not traced,
+// kRayInvalid for every item of an invalid point. The resolve (a wave per point) adds the traced
+// samples' colours in sample order and writes the outputs at the points' input indices (a null one
+// is not written).
+constexpr uint32_t kSampleUntraced = 0xFFFFFFFDu;  // beside kAllSky and kRayInvalid, above any real count
+struct GatherRadianceParams {
+    const DScene* scene;
+    const float* p;        // 3 per point of the call
+    const float* nrm;      // 3 per point of the call
+    uint32_t point0, npoints;
+    uint32_t n;            // npoints x nsamples (< 2^31)
+    uint32_t nsamples, first_sample;
+    int32_t bounce_limit;
+    int32_t hyb_a, hyb_b;
+    int64_t point_base;
+    uint64_t seed;
+    float4_t* q0;     // queue 0 of the workspace (PathParams::q[0])
+    int64_t cap;
+    float4_t* out;    // the result slots (PathParams::out)
+    PathCtl* ctl;
+    PathSort sort;
+    unsigned long long* traced_rays;  // 64 spread counters (a ring slot), or null
+    int32_t* error_flag;
+    float* rgb;
+    float* sum;
+    uint32_t* samples;
+    uint32_t* ray_casts;
+    uint8_t* invalid;
+    float* sample_rgb;     // 3 per item of the call
+    float* dirs;           // 3 per item of the call
+};
+
 // Sample `sample` of point `point` around the unit normal n: bounce_shade's diffuse direction (scan.h)
 // on the (pixel, sample) stream of path_stream. A zero sum gives NaN, which ray_ok rejects.
 ATR_HD V3 gather_dir(uint64_t seed, int64_t point, uint32_t sample, V3 n) {
     uint64_t st, stream;
+    path_stream(seed, point, sample, st, stream);
+    const float r0 = rand_bi(st, stream);
+    const float r1 = rand_bi(st, stream);
+    const float r2 = rand_bi(st, stream);
+    return unit(add(mk(r0, r1, r2), n));
+}
+
+// gather_dir that also hands back the stream after its three draws, for a path that continues on it
+// (atr_gather_radiance): the same draws and the same f32 operations, so the same direction bits.
+ATR_HD V3 gather_dir_state(uint64_t seed, int64_t point, uint32_t sample, V3 n, uint64_t& st, uint64_t& stream) {
     path_stream(seed, point, sample, st, stream);
     const float r0 = rand_bi(st, stream);
     const float r1 = rand_bi(st, stream);

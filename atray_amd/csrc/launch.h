@@ -37,6 +37,9 @@ hipError_t atr_launch_gather(const atr::GatherParams& P, int lane, int ncu, hipS
 // radiance.hip
 hipError_t atr_launch_radiance_entry(const atr::RadianceParams& P, int ncu, hipStream_t s);
 hipError_t atr_launch_radiance_resolve(const atr::RadianceParams& P, hipStream_t s);
+// gather_radiance.hip
+hipError_t atr_launch_gather_radiance_entry(const atr::GatherRadianceParams& P, int ncu, hipStream_t s);
+hipError_t atr_launch_gather_radiance_resolve(const atr::GatherRadianceParams& P, hipStream_t s);
 // plan.hip
 hipError_t atr_launch_plan(const atr::DBlock* base, int32_t nb, unsigned long long* cost,
                            unsigned long long* cost_last, void* work, atr::DBlock* out, int32_t max_split,

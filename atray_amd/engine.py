@@ -111,6 +111,12 @@ class atr_radiance_out(C.Structure):
                 ("traced_rays", C.c_void_p)]
 
 
+class atr_gather_radiance_out(C.Structure):
+    _fields_ = [("rgb", C.c_void_p), ("sum", C.c_void_p), ("samples", C.c_void_p), ("ray_casts", C.c_void_p),
+                ("invalid", C.c_void_p), ("sample_rgb", C.c_void_p), ("dirs", C.c_void_p),
+                ("traced_rays", C.c_void_p)]
+
+
 class atr_tuning(C.Structure):
     _fields_ = [("xcd_chunk", C.c_int32), ("frame_rotate", C.c_int32), ("hybrid_a", C.c_int32),
                 ("hybrid_b", C.c_int32), ("path_batch_log2", C.c_int32), ("cluster_size", C.c_int32),
@@ -138,7 +144,7 @@ EXPORTS = [
     "atr_render_plan_info", "atr_workspace_info", "atr_render_start_samples",
     "atr_render_start_adaptive", "atr_render_adaptive_info", "atr_render_cull_counters",
     "atr_trace_rays", "atr_occluded_rays", "atr_gather_occlusion", "atr_gather_directions",
-    "atr_radiance_rays",
+    "atr_radiance_rays", "atr_gather_radiance",
 ]
 # the diagnostic build's extra symbols (include/atray_diag.h; make -C atray_amd/csrc DIAG=1)
 DIAG_EXPORTS = ["atr_render_wave_trace", "atr_render_phase_clocks", "atr_render_path_counters",
@@ -199,6 +205,8 @@ def lib():
         "atr_gather_directions": ([vp, i64, i32, u32, i64, C.c_uint64, vp, vp], C.c_int),
         "atr_radiance_rays": ([vp, vp, vp, i64, i32, u32, i64, i32, C.c_uint64, P(atr_radiance_out), i32, vp],
                               C.c_int),
+        "atr_gather_radiance": ([vp, vp, vp, i64, i32, u32, i64, i32, C.c_uint64, P(atr_gather_radiance_out), i32,
+                                 vp], C.c_int),
         "atr_render_packed_size": ([vp, i32], i64),
         "atr_render_counters": ([vp, P(atr_camera), vp, i32, C.c_uint64, i32, i64 * 10], C.c_int),
         "atr_render_cull_counters": ([vp, P(atr_camera), vp, i32, C.c_uint64, i32, i64 * 5], C.c_int),
@@ -816,6 +824,74 @@ class Engine:
                                       int(first_sample), int(ray_base), int(bounces),
                                       C.c_uint64(int(seed) & (2**64 - 1)), C.byref(ro), int(sort_bits),
                                       C.c_void_p(stream) if stream else None), "radiance rays")
+        return out, traced
+
+    # atr_gather_radiance_out outputs: name -> (torch dtype name, trailing shape; "s" = nsamples)
+    _GATHER_RADIANCE_OUTPUTS = {"rgb": ("float32", (3,)), "sum": ("float32", (3,)), "samples": ("int32", ()),
+                                "ray_casts": ("int32", ()), "invalid": ("uint8", ()),
+                                "sample_rgb": ("float32", ("s", 3)), "dirs": ("float32", ("s", 3))}
+
+    def gather_radiance(self, points, normals, nsamples, bounces, seed=0, first_sample=0, point_base=0,
+                        sort_bits=-1, start=None, stream=None, want=("rgb", "samples", "invalid")):
+        """atr_gather_radiance: the light arriving at every surface point over its hemisphere, nsamples
+        paths per point, each the renderer's own path after a diffuse hit there (the direction drawn on
+        the device on the stream of (seed, point_base + i, first_sample + s), then at most `bounces`
+        bounces on that stream). points, normals: contiguous (n, 3) float32 tensors on the engine's
+        device (unit normals; a point that is not finite or whose normal is not unit comes back with
+        invalid 1, untraced). `want` names the outputs: rgb, sum (n, 3) float32; samples, ray_casts (n,)
+        int32; invalid (n,) uint8; sample_rgb, dirs (n, nsamples, 3) float32. A later sample range
+        continues an earlier one through `start`, a dict with that call's `sum` and `samples` tensors
+        (required when first_sample > 0) and optionally its `ray_casts`; they are updated in place and
+        returned. Enqueued on `stream` (a raw HIP stream), or torch's current one. Returns ({name:
+        tensor}, the traced-ray count as a one-element int64 tensor); valid once the stream has run,
+        e.g. after wait()."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        for name, a in (("points", points), ("normals", normals)):
+            if not isinstance(a, torch.Tensor) or a.dtype != torch.float32 or a.dim() != 2 or a.shape[1] != 3:
+                raise ValueError(f"{name}: an (n, 3) float32 tensor is required")
+            if a.device != dev:
+                raise ValueError(f"{name}: not on {dev}")
+            if not a.is_contiguous():
+                raise ValueError(f"{name}: not contiguous")
+        if points.shape[0] != normals.shape[0]:
+            raise ValueError("points and normals differ in length")
+        bad = [k for k in want if k not in self._GATHER_RADIANCE_OUTPUTS]
+        if bad:
+            raise ValueError(f"unknown outputs {bad}")
+        n, ns = int(points.shape[0]), int(nsamples)
+        if not 1 <= ns <= 65536:
+            raise ValueError("nsamples: 1..65536")
+
+        def shape(k):
+            return (n,) + tuple(ns if d == "s" else d for d in self._GATHER_RADIANCE_OUTPUTS[k][1])
+
+        given = dict(start or {})
+        bad = [k for k in given if k not in ("sum", "samples", "ray_casts")]
+        if bad:
+            raise ValueError(f"start: unknown entries {bad}")
+        for k, a in given.items():
+            dt = self._GATHER_RADIANCE_OUTPUTS[k][0]
+            if (not isinstance(a, torch.Tensor) or a.dtype != getattr(torch, dt) or a.device != dev
+                    or not a.is_contiguous() or tuple(a.shape) != shape(k)):
+                raise ValueError(f"start[{k!r}]: a contiguous {dt} tensor of {n} points on {dev} is required")
+        if int(first_sample) > 0 and ("sum" not in given or "samples" not in given):
+            raise ValueError("start: sum and samples are required when first_sample > 0")
+        out = {}
+        for k in tuple(want) + tuple(k for k in given if k not in want):
+            out[k] = given[k] if k in given else torch.empty(
+                shape(k), dtype=getattr(torch, self._GATHER_RADIANCE_OUTPUTS[k][0]), device=dev)
+        traced = torch.zeros(1, dtype=torch.int64, device=dev)
+        go = atr_gather_radiance_out(*[out[k].data_ptr() if k in out and n else None
+                                       for k in ("rgb", "sum", "samples", "ray_casts", "invalid", "sample_rgb",
+                                                 "dirs")], traced.data_ptr())
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        check(lib().atr_gather_radiance(self.h, C.c_void_p(points.data_ptr()) if n else None,
+                                        C.c_void_p(normals.data_ptr()) if n else None, n, ns, int(first_sample),
+                                        int(point_base), int(bounces), C.c_uint64(int(seed) & (2**64 - 1)),
+                                        C.byref(go), int(sort_bits), C.c_void_p(stream) if stream else None),
+              "gather radiance")
         return out, traced
 
     def adaptive_info(self):

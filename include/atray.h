@@ -27,7 +27,8 @@ extern "C" {
    change); ABI 1's last two words became path_sort_bits and path_split in round 5.
    atr_trace_rays and atr_ray_hits were added since without a version change: no existing struct
    or entry point changed. atr_occluded_rays likewise; atr_gather_occlusion, atr_gather_out and
-   atr_gather_directions likewise; atr_radiance_rays and atr_radiance_out likewise. */
+   atr_gather_directions likewise; atr_radiance_rays and atr_radiance_out likewise;
+   atr_gather_radiance and atr_gather_radiance_out likewise. */
 #define ATR_ABI_VERSION 2
 
 enum {
@@ -651,6 +652,78 @@ typedef struct {            /* DEVICE pointers; any may be NULL (sum: see above)
 int atr_radiance_rays(atr_ctx* ctx, const float* origins, const float* directions, int64_t nrays,
                       int32_t nsamples, uint32_t first_sample, int64_t ray_base, int32_t bounce_limit,
                       uint64_t seed, const atr_radiance_out* out, int32_t sort_bits, void* stream);
+
+/* Hemisphere radiance gathers (a lightmap or vertex baker, an irradiance probe, a final-gather pass):
+   what light arrives at a surface point over its hemisphere. For npoints surface points with unit
+   normals, nsamples paths per point are started on the device, each one the renderer's own path after
+   a diffuse hit at that point; per point their colours are summed in sample order. No ray array
+   exists anywhere.
+   Sample. Sample s of point i, in separately rounded f32 operations in this order:
+     state, stream = the path stream of (seed, pixel = point_base + i, sample = first_sample + s)
+                     (state = splitmix64(seed ^ pixel ^ sample << 40), increment 2 pixel + 1);
+     r0, r1, r2    = three rand_bi draws, in that order;
+     d             = v * (1 / sqrtf(len2(v))) with v = (r0, r1, r2) + n
+   -- exactly atr_gather_occlusion's and atr_gather_directions' direction, bit for bit. The sample is
+   traced iff the point is valid, (p, d) passes atr_trace_rays' validity test and dot(d, n) > 0:
+   atr_gather_occlusion's rule, so atr_gather_directions' traced_out flags describe this call too. A
+   traced sample's colour is cast_ray(p, d, bounce_limit) (renderer.cpp:213-262) continued on the same
+   stream after those three draws, every f32 operation separately rounded, in cast_ray's order. A
+   sample that is not traced adds to nothing.
+   Point outputs. sum is the traced samples' colours added in sample order; samples counts them;
+   ray_casts adds up cast_ray's bounce counts over them. All three start from 0 when first_sample == 0.
+   When first_sample > 0, sum and samples are required: they are read as the starting values and
+   written back, and ray_casts (if given) is read, added to and written back. rgb = sum /
+   float(samples), or 0,0,0 while samples == 0; not clamped. sample_rgb and dirs are per-call outputs,
+   3 floats per (point, sample) of this call, point-major: written whole, never read; an untraced
+   sample's sample_rgb is 0,0,0, and dirs is the generated direction whether traced or not (as
+   atr_gather_out.dirs).
+   Invalid points. A point is invalid when p is not finite or n fails the direction test
+   (fabsf(len2(n) - 1.0f) <= 0x1p-20f). It traces nothing: its invalid byte is 1, its sample_rgb and
+   dirs rows are zeros; with first_sample == 0 its rgb, sum, samples and ray_casts are written 0, with
+   first_sample > 0 they are left as they are. Its neighbours are untouched; no NaN reaches the
+   traversal.
+   traced_rays accumulates every segment traced: one first segment per traced sample plus the bounce
+   rays. Nothing is shared between samples here, so this is the renderer's count over the same
+   cast_ray calls.
+   Consequences (each is tested):
+     1. samples[i] equals visible[i] + occluded[i] of atr_gather_occlusion with the same points,
+        normals, nsamples, first_sample, point_base and seed and t_max NULL; with bounce_limit == 1,
+        ray_casts[i] equals that call's occluded[i] (an unbounded occlusion query equals closest-hit
+        t < 3.402823466e38, above).
+     2. A batch cut at any point, the second call's point_base advanced by the cut, gives the
+        per-point outputs of one call; a sample range cut in two calls that continue through sum,
+        samples and ray_casts gives the bits of one call, and the sample_rgb and dirs rows concatenate.
+     3. No output bit depends on sort_bits, on the tuning's path_batch_log2, or on the stream.
+   There is deliberately no bit-for-bit tie to a render's pixels: after a diffuse hit the renderer
+   normalises the bounce direction a second time after its lerp, traces directions below the tangent
+   plane too, and carries the surface's weight into the tail's products. The tie is to cast_ray.
+   sort_bits: -1 = the tuning's path_sort_bits, 0 = queue order, 2..7 as for atr_radiance_rays. It
+   orders the bounce levels' queues only; the first segments are traced in (point, sample) order.
+   Ranges, ATR_E_INVALID otherwise: npoints >= 0 and npoints * nsamples < 2^31; nsamples 1..65,536;
+   first_sample + nsamples <= 2^24; point_base >= 0 and point_base + npoints <= 2^32 (the queues carry
+   the stream index in 32 bits); bounce_limit 1..64; sort_bits as above. ATR_E_INVALID also for ctx
+   NULL; for out, points or normals NULL with npoints > 0; for sum or samples NULL with first_sample >
+   0; for all eight pointers of out NULL with npoints > 0. ATR_E_NOSCENE before an upload.
+   npoints == 0: ATR_OK, nothing is enqueued or written.
+   points, normals: DEVICE, 3 floats per point. Asynchronous on `stream`; atr_render_wait covers it
+   (tiles_done 0; a tree-depth flag surfaces as ATR_E_TREE_DEPTH), atr_last_kernel_ms times it. It
+   runs on a path workspace, in batches of whole points of about the tuning's 2^path_batch_log2 paths
+   (at least one point; the tuned size is tried even below 2^16 paths). There is no cell-kernel
+   fallback: if no workspace can be had the call returns -(1000 + hipErrorOutOfMemory) before anything
+   is enqueued, every buffer untouched. No struct and no ABI version change. */
+typedef struct {            /* DEVICE pointers; any may be NULL (sum, samples: see above) */
+    float*    rgb;          /* 3 per point: sum / float(samples), or 0,0,0 while samples == 0; not clamped */
+    float*    sum;          /* 3 per point: running f32 sum of the traced samples' colours, in sample order */
+    uint32_t* samples;      /* per point: traced samples so far (the divisor) */
+    uint32_t* ray_casts;    /* per point: cast_ray's bounce count summed over the traced samples */
+    uint8_t*  invalid;      /* per point: 1 iff the point failed the validity test */
+    float*    sample_rgb;   /* 3 per (point, sample) of THIS call, point-major: the sample's colour; 0,0,0 if untraced */
+    float*    dirs;         /* 3 per (point, sample) of this call: the generated direction (as atr_gather_out.dirs) */
+    unsigned long long* traced_rays;   /* one accumulator */
+} atr_gather_radiance_out;
+int atr_gather_radiance(atr_ctx* ctx, const float* points, const float* normals, int64_t npoints,
+                        int32_t nsamples, uint32_t first_sample, int64_t point_base, int32_t bounce_limit,
+                        uint64_t seed, const atr_gather_radiance_out* out, int32_t sort_bits, void* stream);
 
 /* wait_for_render_from_camera_to_finish: 1 = still running after timeout_ms, 0 = done,
    <0 = error. tiles_done (optional) = tiles of the last render known complete (progress). */
