@@ -294,6 +294,21 @@ struct atr_ctx {
         hipStream_t stream = nullptr;
         bool used = false;
     } query_ws;
+    // Lightmap texels' workspaces (texels.hip), grow-only and apart from the two above. tex_ws
+    // (atr_mesh_texels): `mesh` = the mesh's arrays as the kernels read them, `map` = the face per texel,
+    // `aux` = the scan's block sums and the larger faces' list. The call is synchronous, so nothing of
+    // it is in flight between calls; it still starts with wait_all and records its launches
+    // (note_launch). img_ws (atr_texels_to_image): the dilation's second image and the two flag
+    // arrays; one per context, ordered between streams by `ev` as query_ws is.
+    struct TexelWS {
+        DevBuf mesh, map, aux;
+    } tex_ws;
+    struct ImageWS {
+        DevBuf image, flags;
+        hipEvent_t ev = nullptr;
+        hipStream_t stream = nullptr;
+        bool used = false;
+    } img_ws;
 };
 
 namespace {
@@ -322,6 +337,32 @@ int dev_upload(atr_ctx* c, const void* src, size_t bytes, void** out) {
     c->scene_bytes += int64_t(b.n);
     *out = b.p;
     return ATR_OK;
+}
+
+// A mesh's per-face shading record (renderer.cpp:124-149; DModel::shade, read by shade.h's
+// scene_finish): 9 floats per face, the three vertex normals of a smooth mesh (one that has any
+// normals, renderer.cpp:129) or the three vertices of a flat one. Returns DModel::smooth. The scene
+// upload and atr_mesh_texels both build theirs here, so the texels' normals are the renderer's.
+int32_t shade_records(const HostMesh& M, std::vector<float>& shade) {
+    const int32_t smooth = M.normals.empty() ? 0 : 1;
+    const size_t nf = M.nfaces();
+    shade.assign(9 * (nf ? nf : 1), 0.f);
+    for (size_t f = 0; f < nf; ++f) {
+        for (int k = 0; k < 3; ++k) {
+            V3 v = mk(0.f, 0.f, 0.f);
+            if (smooth) {
+                const int32_t ni = M.face_n[3 * f + size_t(k)];
+                if (ni >= 0 && size_t(ni) < M.normals.size()) v = M.normals[size_t(ni)];
+            } else {
+                const int32_t vi = M.face_v[3 * f + size_t(k)];
+                if (vi >= 0 && size_t(vi) < M.vertices.size()) v = M.vertices[size_t(vi)];
+            }
+            shade[9 * f + 3 * size_t(k)] = v.x;
+            shade[9 * f + 3 * size_t(k) + 1] = v.y;
+            shade[9 * f + 3 * size_t(k) + 2] = v.z;
+        }
+    }
+    return smooth;
 }
 
 // Record on stream s, in a (stream, event) list, that work on s is in flight. Entries whose work
@@ -1335,6 +1376,9 @@ int atr_destroy(atr_ctx* c) {
     if (c->query_ws.rays.p) (void)hipFree(c->query_ws.rays.p);
     if (c->query_ws.bins.p) (void)hipFree(c->query_ws.bins.p);
     if (c->query_ws.ev) (void)hipEventDestroy(c->query_ws.ev);
+    for (DevBuf* d : {&c->tex_ws.mesh, &c->tex_ws.map, &c->tex_ws.aux, &c->img_ws.image, &c->img_ws.flags})
+        if (d->p) (void)hipFree(d->p);
+    if (c->img_ws.ev) (void)hipEventDestroy(c->img_ws.ev);
     for (atr_ctx::PadSlot& q : c->pad_slot) {
         if (q.mem.p) (void)hipFree(q.mem.p);
         if (q.built) (void)hipEventDestroy(q.built);
@@ -1434,24 +1478,8 @@ int atr_scene_upload(atr_ctx* c, const atr_material* mats, int32_t nmats, const 
         dm.nfaces = uint32_t(nf);
         dm.material = md.material;
         std::memcpy(dm.aabb, md.surrounding_aabb, sizeof(dm.aabb));
-        dm.smooth = M.normals.empty() ? 0 : 1;
-        // per-face shading record (renderer.cpp:124-149)
-        std::vector<float> shade(9 * (nf ? nf : 1), 0.f);
-        for (size_t f = 0; f < nf; ++f) {
-            for (int k = 0; k < 3; ++k) {
-                V3 v = mk(0.f, 0.f, 0.f);
-                if (dm.smooth) {
-                    const int32_t ni = M.face_n[3 * f + size_t(k)];
-                    if (ni >= 0 && size_t(ni) < M.normals.size()) v = M.normals[size_t(ni)];
-                } else {
-                    const int32_t vi = M.face_v[3 * f + size_t(k)];
-                    if (vi >= 0 && size_t(vi) < M.vertices.size()) v = M.vertices[size_t(vi)];
-                }
-                shade[9 * f + 3 * size_t(k)] = v.x;
-                shade[9 * f + 3 * size_t(k) + 1] = v.y;
-                shade[9 * f + 3 * size_t(k) + 2] = v.z;
-            }
-        }
+        std::vector<float> shade;
+        dm.smooth = shade_records(M, shade);
         void* p = nullptr;
         int rc = dev_upload(c, shade.data(), shade.size() * sizeof(float), &p);
         if (rc) return rc;
@@ -2496,6 +2524,188 @@ int atr_render_start_progressive(atr_ctx* c, const atr_camera* cam, const atr_ti
 int atr_render_start(atr_ctx* c, const atr_camera* cam, const atr_tile* tiles, int32_t ntiles,
                      const atr_frame* fr, uint64_t seed, void* stream) {
     return atr_render_start_ex(c, cam, tiles, ntiles, fr, seed, stream, ATR_KERNEL_AUTO);
+}
+
+// ------------------------------------------------------------------ lightmap texels (texels.hip)
+namespace {
+// Timing events of one synchronous call, destroyed on every exit path.
+struct EventSet {
+    hipEvent_t e[6] = {};
+    ~EventSet() {
+        for (hipEvent_t x : e)
+            if (x) (void)hipEventDestroy(x);
+    }
+};
+size_t round_up(size_t n, size_t a) { return (n + a - 1) / a * a; }
+}  // namespace
+
+int atr_mesh_texels(atr_ctx* c, const atr_mesh* mesh, int32_t width, int32_t height, int32_t flags, int64_t cap,
+                    const atr_texels_out* out, int64_t* ncovered, float ms_out[2]) {
+    if (!c || !mesh || !out || !ncovered) return ATR_E_INVALID;
+    const HostMesh& M = mesh->m;
+    const size_t nf = M.nfaces();
+    if (M.texcoords.empty() || M.face_t.size() != 3 * nf || nf >= size_t(kTexelNone)) return ATR_E_INVALID;
+    if (width < 1 || width > kTexelMaxSide || height < 1 || height > kTexelMaxSide || cap < 0 ||
+        (flags & ~int32_t(ATR_TEXELS_FLIP)))
+        return ATR_E_INVALID;
+    const auto t0 = std::chrono::steady_clock::now();
+    HIPCHK(hipSetDevice(c->device));
+    // the workspaces are rewritten below: nothing of this context may still be in flight on them
+    HIPCHK(wait_all(c));
+    atr_ctx::TexelWS& ws = c->tex_ws;
+    // the mesh as the kernels read it, in one buffer: the one-model scene of scene_finish, its per-face
+    // 9 floats (the upload's own, shade_records), vertices, texcoords, the two index arrays
+    DScene S;
+    std::memset(&S, 0, sizeof(S));
+    std::vector<float> shade;
+    S.nmodels = 1;
+    S.models[0].smooth = shade_records(M, shade);
+    S.models[0].nfaces = uint32_t(nf);
+    const size_t at_shade = round_up(sizeof(DScene), 256), at_v = at_shade + round_up(shade.size() * 4, 256);
+    const size_t at_t = at_v + round_up(M.vertices.size() * sizeof(V3) + 16, 256);
+    const size_t at_fv = at_t + round_up(M.texcoords.size() * sizeof(V3), 256);
+    const size_t at_ft = at_fv + round_up(3 * nf * 4 + 16, 256), total = at_ft + round_up(3 * nf * 4 + 16, 256);
+    int rc;
+    if ((rc = ensure_buf(ws.mesh, total, false))) return rc;
+    char* const base = static_cast<char*>(ws.mesh.p);
+    S.models[0].shade = reinterpret_cast<const float*>(base + at_shade);
+    std::vector<char> host(total, 0);
+    std::memcpy(host.data(), &S, sizeof(S));
+    std::memcpy(host.data() + at_shade, shade.data(), shade.size() * 4);
+    if (!M.vertices.empty()) std::memcpy(host.data() + at_v, M.vertices.data(), M.vertices.size() * sizeof(V3));
+    std::memcpy(host.data() + at_t, M.texcoords.data(), M.texcoords.size() * sizeof(V3));
+    if (nf) {
+        std::memcpy(host.data() + at_fv, M.face_v.data(), 3 * nf * 4);
+        std::memcpy(host.data() + at_ft, M.face_t.data(), 3 * nf * 4);
+    }
+    HIPCHK(hipMemcpy(base, host.data(), total, hipMemcpyHostToDevice));
+    const size_t ntexels = size_t(width) * size_t(height);
+    const size_t nblocks = (ntexels + kTexelScanBlock - 1) / kTexelScanBlock;
+    const size_t map_bytes = nblocks * kTexelScanBlock * sizeof(uint32_t);
+    if ((rc = ensure_buf(ws.map, map_bytes, false))) return rc;
+    // aux: [0] the list's length; [4 ..] nblocks + 1 sums; then the list, one u32 per face at most
+    if ((rc = ensure_buf(ws.aux, (4 + nblocks + 4 + nf + 4) * sizeof(uint32_t), false))) return rc;
+    TexelParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.mesh.shade = reinterpret_cast<const DScene*>(base);
+    P.mesh.vertices = reinterpret_cast<const float*>(base + at_v);
+    P.mesh.texcoords = reinterpret_cast<const float*>(base + at_t);
+    P.mesh.face_v = reinterpret_cast<const int32_t*>(base + at_fv);
+    P.mesh.face_t = reinterpret_cast<const int32_t*>(base + at_ft);
+    P.mesh.nvertices = uint32_t(M.vertices.size());
+    P.mesh.ntexcoords = uint32_t(M.texcoords.size());
+    P.mesh.nfaces = uint32_t(nf);
+    P.width = width;
+    P.height = height;
+    P.flip = (flags & ATR_TEXELS_FLIP) ? 1 : 0;
+    P.map = static_cast<uint32_t*>(ws.map.p);
+    P.nbig = static_cast<uint32_t*>(ws.aux.p);
+    P.sums = P.nbig + 4;
+    P.nblocks = uint32_t(nblocks);
+    P.big = P.sums + nblocks + 4;
+    P.out = *out;
+    hipStream_t s = c->own_stream;
+    EventSet ev;
+    for (hipEvent_t& e : ev.e) HIPCHK(hipEventCreate(&e));
+    // coverage: the faces with small boxes, and the list of the others
+    HIPCHK(hipEventRecord(ev.e[0], s));
+    HIPCHK(hipMemsetAsync(P.map, 0xFF, map_bytes, s));
+    HIPCHK(hipMemsetAsync(P.nbig, 0, 4 * sizeof(uint32_t), s));
+    HIPCHK(atr_launch_texel_classify(P, s));
+    HIPCHK(hipEventRecord(ev.e[1], s));
+    HIPCHK(note_launch(c, s));
+    uint32_t nbig = 0, count = 0;
+    HIPCHK(hipMemcpyAsync(&nbig, P.nbig, sizeof(nbig), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (nbig > nf) return -(1000 + int(hipErrorUnknown));
+    // the listed faces, then the slot scan
+    HIPCHK(hipEventRecord(ev.e[2], s));
+    HIPCHK(atr_launch_texel_big(P, nbig, s));
+    HIPCHK(atr_launch_texel_scan(P, s));
+    HIPCHK(hipEventRecord(ev.e[3], s));
+    HIPCHK(note_launch(c, s));
+    HIPCHK(hipMemcpyAsync(&count, P.sums + nblocks, sizeof(count), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    *ncovered = int64_t(count);
+    // slots, and the samples when the caller's arrays hold them
+    P.fill = cap >= int64_t(count) ? 1 : 0;
+    const bool write = out->slot || (P.fill && count > 0 && (out->texel || out->face || out->bary || out->point || out->normal));
+    HIPCHK(hipEventRecord(ev.e[4], s));
+    if (write) HIPCHK(atr_launch_texel_write(P, s));
+    HIPCHK(hipEventRecord(ev.e[5], s));
+    HIPCHK(note_launch(c, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (ms_out) {
+        float dev = 0.f;
+        for (int k = 0; k < 6; k += 2) {
+            float ms = 0.f;
+            HIPCHK(hipEventElapsedTime(&ms, ev.e[k], ev.e[k + 1]));
+            dev += ms;
+        }
+        ms_out[0] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        ms_out[1] = dev;
+    }
+    return ATR_OK;
+}
+
+int atr_texels_to_image(atr_ctx* c, const float* values, const int32_t* texel, int64_t ncovered, int32_t width,
+                        int32_t height, int32_t passes, const float fill[3], float* image, void* stream) {
+    if (!c || !image || !fill) return ATR_E_INVALID;
+    if (width < 1 || width > kTexelMaxSide || height < 1 || height > kTexelMaxSide || passes < 0 ||
+        passes > kTexelMaxPasses)
+        return ATR_E_INVALID;
+    const int64_t ntexels = int64_t(width) * int64_t(height);
+    if (ncovered < 0 || ncovered > ntexels || (ncovered > 0 && (!values || !texel))) return ATR_E_INVALID;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = the null stream (HIP convention)
+    atr_ctx::ImageWS& ws = c->img_ws;
+    if (!ws.ev) HIPCHK(hipEventCreateWithFlags(&ws.ev, hipEventDisableTiming));
+    const size_t flag_stride = round_up(size_t(ntexels), 256);
+    const size_t need_image = passes > 0 ? size_t(ntexels) * 3 * sizeof(float) : 0;
+    if (!ws.flags.p || ws.flags.n < 2 * flag_stride || ws.image.n < need_image) {  // grow: after the last call that used it
+        if (ws.used) HIPCHK(hipEventSynchronize(ws.ev));
+        int rc;
+        if ((rc = ensure_buf(ws.flags, 2 * flag_stride, false))) return rc;
+        if (need_image && (rc = ensure_buf(ws.image, need_image, false))) return rc;
+    }
+    if (ws.used && ws.stream != s) HIPCHK(hipStreamWaitEvent(s, ws.ev, 0));
+    c->prog_active = false;
+    HIPCHK(hipEventRecord(c->ev_start, s));
+    ws.used = true;  // from here on kernels of this call may be in flight on s
+    ws.stream = s;
+    // the passes alternate between the caller's image and the workspace's; the last one writes the caller's
+    float* img[2] = {image, static_cast<float*>(ws.image.p)};
+    uint8_t* flg[2] = {static_cast<uint8_t*>(ws.flags.p), static_cast<uint8_t*>(ws.flags.p) + flag_stride};
+    int cur = passes & 1;
+    HIPCHK(hipMemsetAsync(flg[0], 0, size_t(ntexels), s));
+    HIPCHK(atr_launch_texel_scatter(values, texel, ncovered, ntexels, img[cur], flg[0], s));
+    TexelImageParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.width = width;
+    P.height = height;
+    std::memcpy(P.fill, fill, sizeof(P.fill));
+    for (int p = 0; p < passes; ++p) {
+        P.last = p == passes - 1 ? 1 : 0;
+        P.src = img[cur];
+        P.src_flag = flg[p & 1];
+        P.dst = img[cur ^ 1];
+        P.dst_flag = flg[(p & 1) ^ 1];
+        HIPCHK(atr_launch_texel_dilate(P, s));
+        cur ^= 1;
+    }
+    if (passes == 0) {
+        P.last = 1;
+        P.src_flag = flg[0];
+        P.dst = image;
+        HIPCHK(atr_launch_texel_fill(P, s));
+    }
+    HIPCHK(hipEventRecord(ws.ev, s));
+    HIPCHK(record_stop(c, s, nullptr));
+    HIPCHK(note_launch(c, s));
+    c->have_render = true;
+    c->last_stream = s;
+    c->last_ntiles = 0;
+    return ATR_OK;
 }
 
 int atr_render_wait(atr_ctx* c, uint32_t timeout_ms, int32_t* tiles_done) {

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "engine.h"
+#include "texels.h"
 
 extern "C" {
 // render.hip
@@ -40,6 +41,15 @@ hipError_t atr_launch_radiance_resolve(const atr::RadianceParams& P, hipStream_t
 // gather_radiance.hip
 hipError_t atr_launch_gather_radiance_entry(const atr::GatherRadianceParams& P, int ncu, hipStream_t s);
 hipError_t atr_launch_gather_radiance_resolve(const atr::GatherRadianceParams& P, hipStream_t s);
+// texels.hip
+hipError_t atr_launch_texel_classify(const atr::TexelParams& P, hipStream_t s);
+hipError_t atr_launch_texel_big(const atr::TexelParams& P, uint32_t nbig, hipStream_t s);
+hipError_t atr_launch_texel_scan(const atr::TexelParams& P, hipStream_t s);
+hipError_t atr_launch_texel_write(const atr::TexelParams& P, hipStream_t s);
+hipError_t atr_launch_texel_scatter(const float* values, const int32_t* texel, int64_t n, int64_t ntexels, float* image,
+                                    uint8_t* flag, hipStream_t s);
+hipError_t atr_launch_texel_dilate(const atr::TexelImageParams& P, hipStream_t s);
+hipError_t atr_launch_texel_fill(const atr::TexelImageParams& P, hipStream_t s);
 // plan.hip
 hipError_t atr_launch_plan(const atr::DBlock* base, int32_t nb, unsigned long long* cost,
                            unsigned long long* cost_last, void* work, atr::DBlock* out, int32_t max_split,

@@ -38,6 +38,7 @@ MAX_FLOAT = np.float32(3.402823466e38)
 ATR_RAY_SKY, ATR_RAY_TRI, ATR_RAY_SPHERE, ATR_RAY_PLANE, ATR_RAY_INVALID = 0, 1, 2, 3, 4
 # atr_occluded_rays: the byte of a ray
 ATR_OCCL_VISIBLE, ATR_OCCL_OCCLUDED, ATR_OCCL_INVALID = 0, 1, 2
+ATR_TEXELS_FLIP = 1  # atr_mesh_texels: negate every normal
 
 ERRORS = {-1: "ATR_E_INVALID", -2: "ATR_E_IO", -3: "ATR_E_NOMEM", -4: "ATR_E_NOSCENE",
           -5: "ATR_E_TREE_DEPTH", -6: "ATR_E_TREE_LAYOUT"}
@@ -117,6 +118,11 @@ class atr_gather_radiance_out(C.Structure):
                 ("traced_rays", C.c_void_p)]
 
 
+class atr_texels_out(C.Structure):
+    _fields_ = [("slot", C.c_void_p), ("texel", C.c_void_p), ("face", C.c_void_p), ("bary", C.c_void_p),
+                ("point", C.c_void_p), ("normal", C.c_void_p)]
+
+
 class atr_tuning(C.Structure):
     _fields_ = [("xcd_chunk", C.c_int32), ("frame_rotate", C.c_int32), ("hybrid_a", C.c_int32),
                 ("hybrid_b", C.c_int32), ("path_batch_log2", C.c_int32), ("cluster_size", C.c_int32),
@@ -144,7 +150,7 @@ EXPORTS = [
     "atr_render_plan_info", "atr_workspace_info", "atr_render_start_samples",
     "atr_render_start_adaptive", "atr_render_adaptive_info", "atr_render_cull_counters",
     "atr_trace_rays", "atr_occluded_rays", "atr_gather_occlusion", "atr_gather_directions",
-    "atr_radiance_rays", "atr_gather_radiance",
+    "atr_radiance_rays", "atr_gather_radiance", "atr_mesh_texels", "atr_texels_to_image",
 ]
 # the diagnostic build's extra symbols (include/atray_diag.h; make -C atray_amd/csrc DIAG=1)
 DIAG_EXPORTS = ["atr_render_wave_trace", "atr_render_phase_clocks", "atr_render_path_counters",
@@ -207,6 +213,8 @@ def lib():
                               C.c_int),
         "atr_gather_radiance": ([vp, vp, vp, i64, i32, u32, i64, i32, C.c_uint64, P(atr_gather_radiance_out), i32,
                                  vp], C.c_int),
+        "atr_mesh_texels": ([vp, vp, i32, i32, i32, i64, P(atr_texels_out), P(i64), vp], C.c_int),
+        "atr_texels_to_image": ([vp, vp, vp, i64, i32, i32, i32, C.c_float * 3, vp, vp], C.c_int),
         "atr_render_packed_size": ([vp, i32], i64),
         "atr_render_counters": ([vp, P(atr_camera), vp, i32, C.c_uint64, i32, i64 * 10], C.c_int),
         "atr_render_cull_counters": ([vp, P(atr_camera), vp, i32, C.c_uint64, i32, i64 * 5], C.c_int),
@@ -893,6 +901,95 @@ class Engine:
                                         C.byref(go), int(sort_bits), C.c_void_p(stream) if stream else None),
               "gather radiance")
         return out, traced
+
+    # atr_texels_out outputs: name -> (torch dtype name, trailing shape); slot is per texel, the rest per covered k
+    _TEXEL_OUTPUTS = {"slot": ("int32", ()), "texel": ("int32", ()), "face": ("int32", ()), "bary": ("float32", (2,)),
+                      "point": ("float32", (3,)), "normal": ("float32", (3,))}
+
+    def mesh_texels(self, mesh, width, height, flip=False, timings=None):
+        """atr_mesh_texels: one surface sample per texel of `mesh`'s UV layout that a face covers, made on
+        the device (two calls: a size query, then the fill). Returns a dict of tensors on the engine's
+        device: slot (height * width,) int32, the texel's rank k among the covered ones or -1; and per
+        covered k, in ascending texel order, texel (n,) int32 (j * width + i), face (n,) int32, bary
+        (n, 2), point (n, 3) and normal (n, 3) float32 -- point and normal are what the gathers take.
+        flip negates the normals. The mesh is the host Mesh: to bake an uploaded scene, pass the mesh
+        that was uploaded, at the position it was uploaded with. Synchronous: complete on return.
+        timings (a dict, optional) receives wall_ms and device_ms of the second call."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        w, h = int(width), int(height)
+        flags = ATR_TEXELS_FLIP if flip else 0
+        out = {"slot": torch.empty(max(w, 0) * max(h, 0), dtype=torch.int32, device=dev)}
+        n = C.c_int64()
+        torch.cuda.synchronize(dev)  # the call runs on a stream of the context's own
+        check(lib().atr_mesh_texels(self.h, mesh.h, w, h, flags, 0, C.byref(atr_texels_out()), C.byref(n), None),
+              "mesh texels (size)")
+        for k, (dt, tail) in self._TEXEL_OUTPUTS.items():
+            if k != "slot":
+                out[k] = torch.empty((n.value,) + tail, dtype=getattr(torch, dt), device=dev)
+        torch.cuda.synchronize(dev)
+        to = atr_texels_out(*[out[k].data_ptr() if out[k].numel() else None for k in self._TEXEL_OUTPUTS])
+        ms = (C.c_float * 2)()
+        check(lib().atr_mesh_texels(self.h, mesh.h, w, h, flags, n.value, C.byref(to), C.byref(n), ms), "mesh texels")
+        if timings is not None:
+            timings["wall_ms"], timings["device_ms"] = float(ms[0]), float(ms[1])
+        return out
+
+    def texels_to_image(self, values, texel, width, height, passes=2, fill=(0, 0, 0), stream=None):
+        """atr_texels_to_image: per-texel results into a finished lightmap. values: a contiguous (n, 3)
+        float32 tensor, texel: the contiguous (n,) int32 tensor mesh_texels returned (ascending, unique),
+        both on the engine's device. The covered texels get their values, then `passes` (0..64) dilation
+        passes give every empty texel next to a filled one the mean of its filled neighbours, and the
+        texels still empty get `fill`. Enqueued on `stream` (a raw HIP stream), or torch's current one.
+        Returns the image as a (height, width, 3) float32 tensor (row 0 at v near 0); valid once the
+        stream has run, e.g. after wait()."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if (not isinstance(values, torch.Tensor) or values.dtype != torch.float32 or values.dim() != 2
+                or values.shape[1] != 3 or values.device != dev or not values.is_contiguous()):
+            raise ValueError(f"values: a contiguous (n, 3) float32 tensor on {dev} is required")
+        if (not isinstance(texel, torch.Tensor) or texel.dtype != torch.int32 or texel.dim() != 1
+                or texel.device != dev or not texel.is_contiguous()):
+            raise ValueError(f"texel: a contiguous (n,) int32 tensor on {dev} is required")
+        if values.shape[0] != texel.shape[0]:
+            raise ValueError("values and texel differ in length")
+        n, w, h = int(texel.shape[0]), int(width), int(height)
+        image = torch.empty((max(h, 0), max(w, 0), 3), dtype=torch.float32, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        check(lib().atr_texels_to_image(self.h, C.c_void_p(values.data_ptr()) if n else None,
+                                        C.c_void_p(texel.data_ptr()) if n else None, n, w, h, int(passes),
+                                        (C.c_float * 3)(*[float(x) for x in fill]),
+                                        C.c_void_p(image.data_ptr()) if image.numel() else None,
+                                        C.c_void_p(stream) if stream else None), "texels to image")
+        return image
+
+    def bake_lightmap(self, mesh, width, height, nsamples, bounces=None, t_max=None, seed=0, passes=2, flip=False):
+        """A lightmap of `mesh` in three device calls: mesh_texels, a hemisphere gather on the texels'
+        points and normals, texels_to_image. bounces None: gather_occlusion (t_max: one bound for every
+        texel, or None), the value visible / (visible + occluded) on all three channels and 0 where both
+        are 0; an int: gather_radiance's rgb with that many bounces. `mesh` has to be the mesh of the
+        uploaded scene, at the position it was uploaded with: the texels' points are taken from it, the
+        rays are traced in the uploaded scene. Returns (the image as a (height, width, 3) float32 tensor,
+        the texel dict of mesh_texels); on torch's current stream, complete on return."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        tex = self.mesh_texels(mesh, width, height, flip=flip)
+        pts, nrm = tex["point"], tex["normal"]
+        if bounces is None:
+            tm = None if t_max is None else torch.full((pts.shape[0],), float(t_max), dtype=torch.float32, device=dev)
+            out, _ = self.gather_occlusion(pts, nrm, nsamples, t_max=tm, seed=seed)
+            vis, tot = out["visible"].to(torch.float32), (out["visible"] + out["occluded"]).to(torch.float32)
+            val = torch.where(tot > 0, vis / torch.clamp(tot, min=1), torch.zeros_like(vis))
+            values = val[:, None].expand(-1, 3).contiguous()
+        else:
+            out, _ = self.gather_radiance(pts, nrm, nsamples, int(bounces), seed=seed, want=("rgb",))
+            values = out["rgb"]
+        image = self.texels_to_image(values, tex["texel"], width, height, passes=passes)
+        rc, _ = self.wait()
+        check(rc, "bake lightmap")
+        torch.cuda.synchronize(dev)
+        return image, tex
 
     def adaptive_info(self):
         """The last adaptive pass's counts, once wait() returned 0: (pixels live at its start, blocks

@@ -28,7 +28,8 @@ extern "C" {
    atr_trace_rays and atr_ray_hits were added since without a version change: no existing struct
    or entry point changed. atr_occluded_rays likewise; atr_gather_occlusion, atr_gather_out and
    atr_gather_directions likewise; atr_radiance_rays and atr_radiance_out likewise;
-   atr_gather_radiance and atr_gather_radiance_out likewise. */
+   atr_gather_radiance and atr_gather_radiance_out likewise; atr_mesh_texels, atr_texels_out and
+   atr_texels_to_image likewise. */
 #define ATR_ABI_VERSION 2
 
 enum {
@@ -724,6 +725,71 @@ typedef struct {            /* DEVICE pointers; any may be NULL (sum, samples: s
 int atr_gather_radiance(atr_ctx* ctx, const float* points, const float* normals, int64_t npoints,
                         int32_t nsamples, uint32_t first_sample, int64_t point_base, int32_t bounce_limit,
                         uint64_t seed, const atr_gather_radiance_out* out, int32_t sort_bits, void* stream);
+
+/* Lightmap texels: the surface points a lightmap baker feeds to the gathers above, one per texel of
+   the mesh's UV layout, made on the device; atr_texels_to_image turns per-texel results back into an
+   image. Texels, gather, image: a mesh with texture coordinates goes in and a lightmap comes out.
+   Every f32 operation below is separately rounded (tests/c/texel_ref.c restates them in plain C).
+   Texels. A width x height map; texel (i, j) has index j*width + i and the centre
+     p = ((float(i) + 0.5f) / float(width), (float(j) + 0.5f) / float(height)),
+   row 0 at v near 0 (the images' bottom-row-first convention). A texcoord's u, v are the first two of
+   its three floats. Texels exist only inside the map: UVs outside [0, 1) cover nothing.
+   Usable faces. With a, b, c the face's three UVs, a face is usable iff its three texcoord indices are
+   present (>= 0; an index past the array counts as absent), the six floats are finite and
+     area2 = (b.x-a.x)*(c.y-a.y) - (b.y-a.y)*(c.x-a.x)  is neither 0 nor NaN.
+   Coverage. E(p0, p1, p): if (p1.x, p1.y) is lexicographically below (p0.x, p0.y), swap the two and
+   s = -1, else s = 1; E = s * ((p1.x-p0.x)*(p.y-p0.y) - (p1.y-p0.y)*(p.x-p0.x)). Two faces that share
+   an edge compute the same magnitude with opposite signs, so no centre is lost between them. With
+   g = 1 if area2 > 0 else -1:  e0 = g*E(b,c,p), e1 = g*E(c,a,p), e2 = g*E(a,b,p), den = (e0 + e1) + e2;
+   the face covers p iff e0 >= 0 && e1 >= 0 && e2 >= 0 && den > 0. A texel's face is the LOWEST usable
+   face index that covers its centre; a texel no face covers is not covered.
+   Sample of a covered texel: u = e1/den, v = e2/den (the weights of the face's 2nd and 3rd vertex);
+   point = (A + AB*u) + AC*v with AB = B - A, AC = C - A on the face's vertices (a vertex index outside
+   the array reads as the origin, as in atr_scene_upload); normal = the renderer's own for a hit of this
+   face at (u, v): with vertex normals (the mesh has any: atr_scene_upload's rule) unit(na*(1 - u - v) +
+   nb*u + nc*v), else unit(cross(v0 - v1, v0 - v2)); ATR_TEXELS_FLIP negates it (a mesh wound the other
+   way round). A degenerate normal (NaN) is passed through: the gathers call such a point invalid and
+   leave its neighbours alone.
+   Outputs. slot is per texel; the others are per covered texel k, k ascending with the texel index
+   (so texel[] is ascending and slot[texel[k]] == k). *ncovered always receives the count. If cap <
+   count the per-k arrays are left untouched and slot is still written: a size query (the pattern of
+   atr_render_plan_info); call again with arrays of `count` elements.
+   A set-up call, synchronous like atr_scene_upload and atr_octree_build_device: it runs on a stream
+   of the context's own and every output is complete on return; the caller's earlier work on the
+   output buffers must have finished. `mesh` is the host mesh; what the kernels read of it is copied
+   into a grow-only texel workspace of the context (apart from the query and path workspaces; with the
+   face map 4 B per texel), after waiting for everything the context has in flight. To bake an
+   uploaded scene, pass the mesh that was uploaded, at the position it was uploaded with. No scene is
+   needed. ms_out (may be NULL): [0] wall time of the call, [1] device time of its kernels.
+   ATR_E_INVALID: ctx, mesh, out or ncovered NULL; a mesh without texcoords; width or height outside
+   1..16,384; cap < 0; unknown flag bits. No struct and no ABI version change. */
+enum { ATR_TEXELS_FLIP = 1 };       /* negate every normal */
+typedef struct {                    /* DEVICE pointers; any may be NULL */
+    int32_t*  slot;    /* width*height: rank k of the texel among the covered ones, or -1 */
+    int32_t*  texel;   /* per covered k (ascending texel index): j*width + i */
+    uint32_t* face;    /* per k: the covering face */
+    float*    bary;    /* 2 per k: u, v */
+    float*    point;   /* 3 per k */
+    float*    normal;  /* 3 per k, unit */
+} atr_texels_out;
+int atr_mesh_texels(atr_ctx* ctx, const atr_mesh* mesh, int32_t width, int32_t height, int32_t flags,
+                    int64_t cap, const atr_texels_out* out, int64_t* ncovered, float ms_out[2]);
+/* Per-texel results into a finished lightmap: image[texel[k]] = values[k] (3 floats each), every other
+   texel empty; then `passes` (0..64) dilation passes, each reading only the state at its start: an
+   empty texel with n >= 1 non-empty texels among its 8 neighbours inside the map gets, per channel,
+   ((0 + v_1) + ... + v_n) / float(n), the neighbours taken in the order dy = -1..1, dx = -1..1, and is
+   non-empty from the next pass on; after the last pass the texels still empty get `fill` (HOST, 3
+   floats). `image` (3 floats per texel, row 0 at the bottom) is written whole and must not overlap
+   `values`. values, texel, image: DEVICE. texel must be ascending and unique, as atr_mesh_texels wrote
+   it; that is the caller's to keep and is not checked (an index outside the map is skipped).
+   Asynchronous on `stream`; atr_render_wait covers it (tiles_done 0), atr_last_kernel_ms times it.
+   The passes ping-pong between `image` and a grow-only image workspace of the context (14 B per
+   texel), which a call on another stream than the last first waits for on the GPU.
+   ATR_E_INVALID: ctx, image or fill NULL; values or texel NULL with ncovered > 0; ncovered < 0 or >
+   width*height; width or height outside 1..16,384; passes outside 0..64. */
+int atr_texels_to_image(atr_ctx* ctx, const float* values, const int32_t* texel, int64_t ncovered,
+                        int32_t width, int32_t height, int32_t passes, const float fill[3], float* image,
+                        void* stream);
 
 /* wait_for_render_from_camera_to_finish: 1 = still running after timeout_ms, 0 = done,
    <0 = error. tiles_done (optional) = tiles of the last render known complete (progress). */
