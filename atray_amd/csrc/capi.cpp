@@ -269,6 +269,7 @@ struct atr_ctx {
         DevBuf mem;
         uint64_t gen = 0;  // scene_gen of the table's scene; 0: empty
         int32_t rows = 0;
+        bool wide = false;  // a COUNT launch's table: two pairs per cluster (cluster.h pads_entry)
         float eye[kMaxFrameCams][3];
         hipEvent_t built = nullptr;
         hipStream_t built_on = nullptr;
@@ -280,6 +281,8 @@ struct atr_ctx {
     PadSlot pad_slot[kPadSlots];
     uint64_t pad_clock = 0, scene_gen = 0;
     bool camera_pads = true;
+    // ATR_FACING_FOLD at atr_create (0 = the table holds the unfolded loose growths; cluster.h fold_box)
+    bool facing_fold = true;
     // ATR_WAVE_CULL at atr_create (0 = the primary kernels test every cluster of a leaf per ray)
     bool wave_cull = true;
     // Ray queries' workspace (atr_trace_rays, query.hip), apart from the path workspaces and grow-only:
@@ -944,7 +947,9 @@ hipError_t bind_pads(atr_ctx* c, RenderParams& P, int sched, hipStream_t s, atr_
     const int32_t rows = P.nfcam > 0 ? P.nfcam : 1;
     if (rows > kMaxFrameCams) return hipSuccess;
     const int32_t stride = int32_t(c->nclusters);
-    const size_t bytes = size_t(rows) * size_t(stride) * sizeof(float2_t);
+    // an instrumented launch reads the unfolded pair and the folded growth: a table of its own kind
+    const bool wide = P.counters != nullptr;
+    const size_t bytes = size_t(rows) * size_t(stride) * sizeof(float2_t) * (wide ? 2 : 1);
     if (bytes > atr_ctx::kPadMaxBytes) return hipSuccess;
     PadEyes eyes;
     std::memset(&eyes, 0, sizeof(eyes));
@@ -956,7 +961,7 @@ hipError_t bind_pads(atr_ctx* c, RenderParams& P, int sched, hipStream_t s, atr_
     atr_ctx::PadSlot* sl = nullptr;
     atr_ctx::PadSlot* lru = &c->pad_slot[0];
     for (atr_ctx::PadSlot& q : c->pad_slot) {
-        if (q.gen == c->scene_gen && q.rows == rows && std::memcmp(q.eye, eyes.e, sizeof(float) * 3 * size_t(rows)) == 0) {
+        if (q.gen == c->scene_gen && q.rows == rows && q.wide == wide && std::memcmp(q.eye, eyes.e, sizeof(float) * 3 * size_t(rows)) == 0) {
             sl = &q;
             break;
         }
@@ -987,12 +992,14 @@ hipError_t bind_pads(atr_ctx* c, RenderParams& P, int sched, hipStream_t s, atr_
                 if (se.first != s && (e = hipStreamWaitEvent(s, se.second, 0)) != hipSuccess) return e;
         }
         sl->gen = 0;  // stays empty if the build cannot be enqueued
-        if ((e = atr_launch_camera_pads(c->d_scene, eyes, rows, stride, static_cast<float2_t*>(sl->mem.p), s)) != hipSuccess)
+        if ((e = atr_launch_camera_pads(c->d_scene, eyes, rows, stride, c->facing_fold, wide, static_cast<float2_t*>(sl->mem.p),
+                                        nullptr, nullptr, nullptr, s)) != hipSuccess)
             return e;
         if ((e = hipEventRecord(sl->built, s)) != hipSuccess) return e;
         sl->built_on = s;
         sl->gen = c->scene_gen;
         sl->rows = rows;
+        sl->wide = wide;
         std::memcpy(sl->eye, eyes.e, sizeof(eyes.e));
     }
     sl->last_use = ++c->pad_clock;
@@ -1298,6 +1305,9 @@ int atr_create(int device, atr_ctx** out) {
     // ATR_WAVE_CULL=0: this context's primary kernels skip the wave cull of a leaf's clusters (A/B runs
     // and the tests that compare the two); unset or anything else: they cull
     if (const char* v = std::getenv("ATR_WAVE_CULL")) c->wave_cull = !(v[0] == '0' && v[1] == '\0');
+    // ATR_FACING_FOLD=0: this context's table holds the unfolded loose growths (A/B runs and tests; same
+    // output bits either way)
+    if (const char* v = std::getenv("ATR_FACING_FOLD")) c->facing_fold = !(v[0] == '0' && v[1] == '\0');
     const int rc = [&]() -> int {  // any failure below releases what was created (atr_destroy)
         HIPCHK(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
         HIPCHK(hipEventCreate(&c->ev_start));
@@ -2365,6 +2375,65 @@ int atr_render_cull_counters(atr_ctx* c, const atr_camera* cam, const atr_tile* 
     out[2] = int64_t(h[25]);  // dealt rounds
     out[3] = int64_t(h[26]);  // dealt items
     return ATR_OK;
+}
+
+int atr_render_fold_counters(atr_ctx* c, const atr_camera* cam, const atr_tile* tiles, int32_t ntiles,
+                             uint64_t seed, int32_t variant, int64_t out[2]) {
+    if (!out) return ATR_E_INVALID;
+    unsigned long long h[kCounterSlots];
+    const int rc = count_launch(c, cam, tiles, ntiles, seed, variant, h);
+    if (rc != ATR_OK) return rc;
+    out[0] = int64_t(h[30]);  // (ray, cluster) pairs past the unfolded loose box that fail the folded one
+    out[1] = int64_t(h[31]);  // the primitives screened for them
+    return ATR_OK;
+}
+
+int64_t atr_camera_pads_row(atr_ctx* c, const float eye[3], float* row, float* boxes, float* edges, int64_t cap) {
+    if (!c || !eye || cap < 0) return ATR_E_INVALID;
+    if (!c->d_scene) return ATR_E_NOSCENE;
+    const int64_t n = c->nclusters;
+    if (n <= 0 || n > int64_t(1) << 30) return n <= 0 ? 0 : ATR_E_INVALID;
+    if (!row || cap < n) return n;  // the count alone
+    HIPCHK(hipSetDevice(c->device));
+    PadEyes eyes;
+    std::memset(&eyes, 0, sizeof(eyes));
+    eyes.e[0][0] = eye[0], eyes.e[0][1] = eye[1], eyes.e[0][2] = eye[2];
+    // the table row as bind_pads builds it for a one-camera launch of this context (the same kernel,
+    // the same arguments), with the fold kernel's side outputs; without the fold the row comes from
+    // camera_pads_kernel and the side outputs from a second launch into a table of their own
+    const size_t nn = size_t(n);
+    DevTmp d_tab, d_info, d_box, d_edge, d_tab2;
+    HIPCHK(hipMalloc(&d_tab.p, nn * sizeof(float2_t)));
+    HIPCHK(hipMalloc(&d_info.p, nn * sizeof(float2_t)));
+    HIPCHK(hipMalloc(&d_box.p, nn * 3 * sizeof(float4_t)));
+    HIPCHK(hipMalloc(&d_edge.p, nn * 96 * sizeof(float)));
+    HIPCHK(hipMemset(d_tab.p, 0, nn * sizeof(float2_t)));  // (an entry no tree model covers reads back as 0)
+    HIPCHK(hipMemset(d_info.p, 0, nn * sizeof(float2_t)));
+    HIPCHK(hipMemset(d_box.p, 0, nn * 3 * sizeof(float4_t)));
+    HIPCHK(hipMemset(d_edge.p, 0, nn * 96 * sizeof(float)));
+    float2_t* const tab = static_cast<float2_t*>(d_tab.p);
+    float2_t* const info = static_cast<float2_t*>(d_info.p);
+    float4_t* const box = static_cast<float4_t*>(d_box.p);
+    float* const edge = static_cast<float*>(d_edge.p);
+    if (c->facing_fold) {
+        HIPCHK(atr_launch_camera_pads(c->d_scene, eyes, 1, int32_t(n), 1, 0, tab, info, box, edge, nullptr));
+    } else {
+        HIPCHK(atr_launch_camera_pads(c->d_scene, eyes, 1, int32_t(n), 0, 0, tab, nullptr, nullptr, nullptr, nullptr));
+        HIPCHK(hipMalloc(&d_tab2.p, nn * sizeof(float2_t)));
+        HIPCHK(atr_launch_camera_pads(c->d_scene, eyes, 1, int32_t(n), 0, 0, static_cast<float2_t*>(d_tab2.p), info, box,
+                                      edge, nullptr));
+    }
+    HIPCHK(hipDeviceSynchronize());
+    std::vector<float2_t> h_tab(nn), h_info(nn);
+    HIPCHK(hipMemcpy(h_tab.data(), d_tab.p, nn * sizeof(float2_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(h_info.data(), d_info.p, nn * sizeof(float2_t), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < nn; ++i) {
+        row[4 * i] = h_tab[i].x, row[4 * i + 1] = h_tab[i].y;
+        row[4 * i + 2] = h_info[i].x, row[4 * i + 3] = h_info[i].y;
+    }
+    if (boxes) HIPCHK(hipMemcpy(boxes, d_box.p, nn * 3 * sizeof(float4_t), hipMemcpyDeviceToHost));
+    if (edges) HIPCHK(hipMemcpy(edges, d_edge.p, nn * 96 * sizeof(float), hipMemcpyDeviceToHost));
+    return n;
 }
 
 #ifdef ATR_DIAG

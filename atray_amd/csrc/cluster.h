@@ -91,6 +91,102 @@ __device__ __forceinline__ float2_t cluster_grow(V3 o, float4_t lo, float4_t hi)
     return g;
 }
 
+// The det floor of a (camera, cluster) pair (the facing fold): a delta in
+// [kTol, kTau] such that, for every ray from `eye` that accepts a primitive of the cluster, that
+// primitive's computed det is >= delta. The loose growth may then be sized for det >= delta instead
+// of det >= kTol (cluster_grow_fold): camera_pads_kernel stores that growth where the primary
+// kernels read the loose one. Evaluated in f64 (the table kernel is no hot path), so that the
+// rounding of the bound itself is far below its margin.
+//
+//   * The rays. A ray (eye, d) that accepts a primitive has computed det >= kTol, so by the rounding
+//     bound above its true line passes within W (29 eps P / kTol + 6 eps) <= gl of the triangle, at
+//     a parameter within that distance of the computed t. B = the cluster box grown per axis by
+//     gl (1 + 2^-10) + 2^-20 F_axis (F = the far face's distance from the eye: the f32 slab test's
+//     own rounding, with room). With the eye outside B -- required here as r_min > r_max / 1024,
+//     r_min and r_max the distances from the eye to B and to its far corner -- that point p of the
+//     line lies in B at a positive parameter: d = |d| (p - eye) / |p - eye|.
+//   * The bound. With N = ab x ac, s(p) = -(p - eye) . N is affine in p: over B its extremes are
+//     per axis at one of the two faces. The true det -(d . N) = |d| s(p) / |p - eye| then lies in
+//     [L, U] |d| with L = s_min / (s_min >= 0 ? r_max : r_min), U = s_max / (s_max >= 0 ? r_min : r_max).
+//   * The margin m = 32 eps P, P >= |ab||ac| >= |N| the cluster's bound: 16 eps P between -(d . N)
+//     and the computed det (what the screen uses, cluster_pads); 8 eps P for |d| = 1 +- 4.5 eps
+//     (unit(): three products and two adds, a square root, a division, a product); 8 eps P for the
+//     evaluation here: f32 products are exact in f64 and N's differences round by 2^-53 |ab||ac|,
+//     the sums of s by a few 2^-53 r_max P, the square roots and quotients by 2^-52 relative, and
+//     r_max / r_min <= 1024, so the whole is below 2^-38 P.
+//   * A primitive with U < kTol - m is rejected by the culled test for every such ray and takes no
+//     part. Otherwise computed det >= L - m; delta = clamp(min L - m, kTol, kTau), rounded down to
+//     f32. NaN or infinite operands give comparisons that are false: not rejected, delta = kTol.
+struct FoldBox {
+    double x0[3], x1[3];  // B's faces relative to the eye
+    double rmin, rmax;
+    bool ok;  // finite operands, the eye clearly outside B, a usable screen step
+};
+__device__ __forceinline__ FoldBox fold_box(V3 eye, float4_t lo, float4_t hi, float gl) {
+    FoldBox b;
+    const double l[3] = {lo.x, lo.y, lo.z}, h[3] = {hi.x, hi.y, hi.z}, e[3] = {eye.x, eye.y, eye.z};
+    const double g = double(gl) * (1.0 + 0x1p-10);
+    double n2 = 0.0, f2 = 0.0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const double F = fmax(fabs(l[a] - e[a]), fabs(h[a] - e[a]));
+        const double slack = g + 0x1p-20 * F;
+        b.x0[a] = l[a] - e[a] - slack;
+        b.x1[a] = h[a] - e[a] + slack;
+        const double nr = fmax(fmax(b.x0[a], -b.x1[a]), 0.0), fr = fmax(fabs(b.x0[a]), fabs(b.x1[a]));
+        n2 += nr * nr;
+        f2 += fr * fr;
+    }
+    b.rmin = sqrt(n2);
+    b.rmax = sqrt(f2);
+    // f2 finite: every operand was; hi.w: a zero or subnormal screen step means no screen
+    b.ok = f2 < double(__builtin_inff()) && b.rmin > b.rmax * 0x1p-10 && hi.w >= 1.1754944e-38f;
+    return b;
+}
+
+// One primitive's part: rejected for every ray of the cone (true), or its lower bound less the margin.
+__device__ __forceinline__ bool fold_prim(const FoldBox& b, float P, float4_t a0, float4_t a1, float4_t a2,
+                                          double& lower) {
+    const double abx = a0.w, aby = a1.x, abz = a1.y, acx = a1.z, acy = a1.w, acz = a2.x;
+    const double N[3] = {aby * acz - abz * acy, abz * acx - abx * acz, abx * acy - aby * acx};
+    double smin = 0.0, smax = 0.0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const double u = -b.x0[a] * N[a], v = -b.x1[a] * N[a];
+        smin += fmin(u, v);
+        smax += fmax(u, v);
+    }
+    const double m = 32.0 * double(kEps) * double(P);
+    const double L = smin / (smin >= 0.0 ? b.rmax : b.rmin), U = smax / (smax >= 0.0 ? b.rmin : b.rmax);
+    lower = L - m;
+    if (!(lower == lower)) lower = -double(__builtin_inff());
+    return U < double(kTol) - m;
+}
+
+// delta from the smallest lower bound of the primitives that take part (+inf: none does).
+__device__ __forceinline__ float fold_delta(double lower) {
+    if (!(lower > double(kTol))) return kTol;
+    if (lower >= double(kTau)) return kTau;
+    float d = float(lower);
+    if (double(d) > lower) d = __uint_as_float(__float_as_uint(d) - 1u);  // positive: the float below
+    return fmaxf(d, kTol);
+}
+
+// cluster_grow's loose growth for det >= delta (kTol <= delta <= kTau): the same W and P and the
+// same order of operations, delta in kTol's place; g = cluster_grow's pair. delta = kTol returns
+// g.x itself, and the result never falls below the tight growth.
+__device__ __forceinline__ float cluster_grow_fold(V3 o, float4_t lo, float4_t hi, float delta, float2_t g) {
+    if (!(delta > kTol)) return g.x;
+    const float ex = hi.x - lo.x, ey = hi.y - lo.y, ez = hi.z - lo.z;
+    const float fx = fmaxf(fabsf(lo.x - o.x), fabsf(hi.x - o.x));
+    const float fy = fmaxf(fabsf(lo.y - o.y), fabsf(hi.y - o.y));
+    const float fz = fmaxf(fabsf(lo.z - o.z), fabsf(hi.z - o.z));
+    const float W = (__builtin_amdgcn_sqrtf(fx * fx + fy * fy + fz * fz) + 1.0842022e-19f) * 1.0000005f + (ex + ey + ez);
+    const float P = lo.w;
+    const float gf = W * (P * (kPadRel / (0.9f * delta)) + kPadAbs);  // IEEE division
+    return fminf(fmaxf(gf, g.y), g.x);
+}
+
 // Cluster record lo, hi and its growths g (cluster_grow): the two rounding-padded box
 // tests. False: no primitive inside can be accepted with t <= best. Else the det band
 // [dlo, dhi) of the primitives that still need the full test.
@@ -206,6 +302,12 @@ __device__ __forceinline__ uint32_t screen8(const ScreenRay& sr, float blo, floa
 }
 #endif
 
+// The table's entry of cluster c (RenderParams::pads): one pair per cluster, {folded loose, tight}, in
+// the tables the product kernels read; two in the COUNT launches' tables, {unfolded loose, tight}
+// {folded loose, det floor}, so the COUNT build's tests read what the table kernel wrote for them.
+template <bool COUNT>
+__device__ __forceinline__ size_t pads_entry(size_t c) { return COUNT ? 2 * c : c; }
+
 // Cluster c of a leaf: the padded box tests and the screen against the bound `best`. Returns the
 // mask of the primitives (slot 16 c + bit) that still need the full test.
 // PADS: the growths of the box come from the camera's table row `pads` (indexed by the model's
@@ -213,8 +315,9 @@ __device__ __forceinline__ uint32_t screen8(const ScreenRay& sr, float blo, floa
 template <bool COUNT, bool EARLY = true, bool PADS = false>
 __device__ __forceinline__ uint32_t cluster_cands(const Ray& r, const DModel& m, uint32_t c, float4_t lo, float4_t hi,
                                                   float best, Ctr& ct, const float2_t* pads = nullptr) {
+    // (the COUNT build's table is wide, pads_entry below: the unfolded pair, then the folded growth)
     float2_t g;
-    if constexpr (PADS) g = pads[c];
+    if constexpr (PADS) g = pads[pads_entry<COUNT>(c)];
     // the screen constants (7 values) are recomputed for every cluster from an opaque copy of the
     // ray instead of being hoisted out of the scan loops and held through the passes and rounds:
     // ~10 VALU per cluster for 7 VGPRs, what lets HYBRID run 6 waves/SIMD
@@ -229,11 +332,20 @@ __device__ __forceinline__ uint32_t cluster_cands(const Ray& r, const DModel& m,
     if constexpr (EARLY) {
         e0 = nb[0], e1 = nb[1], ez = nb[kMaxClusterSize / 4];
     }
+    // The COUNT build goes on counting the unfolded loose box's work (its counters are compared with
+    // the inline kernels'): its table holds the unfolded pair too, written by the table kernel next to
+    // the folded growth, which it tests only to count what the product kernels no longer do.
+    [[maybe_unused]] float2_t gfold;
+    if constexpr (PADS && COUNT) gfold = float2_t{pads[pads_entry<COUNT>(c) + 1].x, g.y};
     if constexpr (!PADS) g = cluster_grow(r.o, lo, hi);
     float dlo, dhi;
     if (!cluster_pads(r, sr, lo, hi, g, best, dlo, dhi)) return 0;
     const uint32_t n = (__float_as_uint(lo.w) & 31u) + 1u;
     if constexpr (COUNT) ct.screen += n;
+    if constexpr (PADS && COUNT) {
+        float fl, fh;
+        if (!cluster_pads(r, sr, lo, hi, gfold, best, fl, fh)) { ct.fold_box += 1; ct.fold_screen += n; }
+    }
     const uint32_t slots = (2u << (n - 1)) - 1u;  // [0, n), 1 <= n <= 16
     const float q = hi.w;
     if (!(q >= 1.1754944e-38f)) return slots;  // zero or subnormal step (degenerate normals): no screen

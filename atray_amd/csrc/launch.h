@@ -11,7 +11,8 @@ extern "C" {
 hipError_t atr_launch_render(const atr::RenderParams& P, int sched, int primary_occ, hipStream_t s);
 int atr_render_reads_pads(const atr::RenderParams& P, int sched);
 hipError_t atr_launch_camera_pads(const atr::DScene* scene, const atr::PadEyes& eyes, int32_t nrows, int32_t stride,
-                                  atr::float2_t* table, hipStream_t s);
+                                  int fold, int wide, atr::float2_t* table, atr::float2_t* info, atr::float4_t* boxes,
+                                  float* edges, hipStream_t s);
 hipError_t atr_launch_traced_finish(unsigned long long* slots, unsigned long long* out, hipStream_t s);
 hipError_t atr_launch_unpack(const atr::DBlock* blocks, int32_t nblocks, int32_t width, const uint32_t* packed,
                              uint32_t* image, hipStream_t s);

@@ -174,7 +174,7 @@ __global__ __launch_bounds__(256, OCC) void render_kernel(RenderParams P) {
         if constexpr (PADS) {
             // the camera's row: the frame index and the stride are wave-uniform, the base stays in SGPRs
             const int32_t row = P.nfcam > 0 ? __builtin_amdgcn_readfirstlane(fidx) : 0;
-            const float2_t* pads = uniform_global(P.pads) + int64_t(row) * P.pads_stride;
+            const float2_t* pads = uniform_global(P.pads) + pads_entry<COUNT>(size_t(int64_t(row) * P.pads_stride));
             intersect_scene<SCHED, FlavPrimaryPads, COUNT>(S, eye, dir, active, id, err, ct, P.hyb_a, P.hyb_b, pads,
                                                            P.wave_cull);
         } else {
@@ -304,6 +304,18 @@ __global__ __launch_bounds__(256, OCC) void render_kernel(RenderParams P) {
             for (int off = 32; off > 0; off >>= 1) x2 += __shfl_xor(x2, off);
             if (lane == 0 && x2) atomicAdd(C + 29, (unsigned long long)x2);
         }
+        // counters[30..31] (the table build): what the facing fold removes from the product kernels,
+        // (ray, cluster) pairs past the loose box and the primitives screened for them
+        if constexpr (PADS) {
+            uint32_t f[2] = {ct.fold_box, ct.fold_screen};
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                uint32_t x2 = f[k];
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) x2 += __shfl_xor(x2, off);
+                if (lane == 0 && x2) atomicAdd(C + 30 + k, (unsigned long long)x2);
+            }
+        }
         // counters[10..15]: wave clocks in DFS passes, lane-private scans, dealt rounds, whole
         // wave, per-step preparation, whole FLAT/HYBRID scan (phases: diagnostic build only)
         if (lane == 0) {
@@ -345,6 +357,9 @@ template __global__ void render_kernel<SCHED_HYBRID, true, true, 4, false, true>
 // The table of box growths (RenderParams::pads): thread (x, y) computes the pair of scene cluster x
 // for camera y's eye -- cluster_grow, the function the inline path evaluates per (ray, cluster) --
 // and writes table[y * stride + x]. stride = the scene's cluster count (DModel::cl_base / cl_count).
+// WIDE (a COUNT launch's table, cluster.h pads_entry): two pairs per cluster, the second the folded
+// growth and the det floor -- here, without the fold, the loose growth again and kTol.
+template <bool WIDE>
 __global__ __launch_bounds__(256) void camera_pads_kernel(const DScene* __restrict__ S, PadEyes eyes, int32_t stride,
                                                           float2_t* __restrict__ table) {
     const uint32_t x = blockIdx.x * 256u + threadIdx.x;
@@ -356,8 +371,82 @@ __global__ __launch_bounds__(256) void camera_pads_kernel(const DScene* __restri
         const DModel& m = S->models[i];
         const uint32_t c = x - m.cl_base;  // wraps below the model's first cluster
         if (!m.has_tree || c >= m.cl_count) continue;
-        table[size_t(f) * size_t(stride) + x] =
-            cluster_grow(eye, m.clus[kClusterBlock * size_t(c)], m.clus[kClusterBlock * size_t(c) + 1]);
+        const float2_t g = cluster_grow(eye, m.clus[kClusterBlock * size_t(c)], m.clus[kClusterBlock * size_t(c) + 1]);
+        const size_t e = size_t(f) * size_t(stride) + x;
+        if constexpr (WIDE) {
+            table[2 * e] = g;
+            table[2 * e + 1] = float2_t{g.x, kTol};
+        } else {
+            table[e] = g;
+        }
+        return;
+    }
+}
+
+// The same table with the facing fold (cluster.h fold_box): entry {folded loose growth, tight growth};
+// WIDE: {unfolded loose, tight}{folded loose, det floor}. Sixteen lanes per cluster, one primitive
+// each, read once and kept (its operands do not depend on the camera); the rows are a loop inside,
+// the smallest lower bound a minimum over the sixteen lanes, and lane 0 of them writes the entry. A
+// group's lanes share their cluster, so they leave and loop together. fold = 0: delta = kTol, the
+// unfolded pair (atr_camera_pads_row's side outputs in a context without the fold).
+// Side outputs for atr_camera_pads_row (one row; each may be null), written by the launch that
+// writes the table: `info` {delta, bits(mask of the primitives treated as rejected)} per cluster,
+// `boxes` the cluster's two record words with the unfolded loose growth in a third ({lo.xyz, P}
+// {hi.xyz, q}{loose, 0, 0, 0}), `edges` ab and ac of its 16 slots (0 past its count).
+template <bool WIDE>
+__global__ __launch_bounds__(256) void camera_fold_kernel(const DScene* __restrict__ S, PadEyes eyes, int32_t nrows,
+                                                          int32_t stride, int32_t fold, float2_t* __restrict__ table,
+                                                          float2_t* __restrict__ info, float4_t* __restrict__ boxes,
+                                                          float* __restrict__ edges) {
+    static_assert(kMaxClusterSize == 16, "sixteen lanes per cluster");
+    const uint32_t x = blockIdx.x * 16u + (threadIdx.x >> 4), j = threadIdx.x & 15u;
+    if (x >= uint32_t(stride)) return;
+    const int32_t nmodels = S->nmodels;
+    for (int32_t i = 0; i < nmodels; ++i) {
+        const DModel& m = S->models[i];
+        const uint32_t c = x - m.cl_base;  // wraps below the model's first cluster
+        if (!m.has_tree || c >= m.cl_count) continue;
+        const float4_t lo = m.clus[kClusterBlock * size_t(c)], hi = m.clus[kClusterBlock * size_t(c) + 1];
+        const uint32_t n = (__float_as_uint(lo.w) & 31u) + 1u;
+        const bool have = j < n;
+        float4_t a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0, a2 = a0;
+        if (have) load_prim(m, kMaxClusterSize * c + j, a0, a1, a2);
+        for (int32_t f = 0; f < nrows; ++f) {
+            const V3 eye = mk(eyes.e[f][0], eyes.e[f][1], eyes.e[f][2]);
+            const float2_t g = cluster_grow(eye, lo, hi);
+            const FoldBox b = fold_box(eye, lo, hi, g.x);
+            double lower = double(__builtin_inff());
+            bool rej = false;
+            if (have) {
+                rej = fold_prim(b, lo.w, a0, a1, a2, lower);
+                if (rej) lower = double(__builtin_inff());
+            }
+            const uint32_t mask = uint32_t(__ballot(rej) >> (threadIdx.x & 48u)) & 0xFFFFu;
+#pragma unroll
+            for (int off = 8; off > 0; off >>= 1) lower = fmin(lower, __shfl_xor(lower, off));
+            const bool folded = fold && b.ok;
+            const float delta = folded ? fold_delta(lower) : kTol;
+            const float gf = cluster_grow_fold(eye, lo, hi, delta, g);
+            if (j == 0) {
+                const size_t e = size_t(f) * size_t(stride) + x;
+                if constexpr (WIDE) {
+                    table[2 * e] = g;
+                    table[2 * e + 1] = float2_t{gf, delta};
+                } else {
+                    table[e] = float2_t{gf, g.y};
+                }
+                if (info) info[x] = float2_t{delta, __uint_as_float(folded ? mask : 0u)};
+                if (boxes) {
+                    boxes[3 * size_t(x)] = lo;
+                    boxes[3 * size_t(x) + 1] = hi;
+                    boxes[3 * size_t(x) + 2] = float4_t{g.x, 0.f, 0.f, 0.f};
+                }
+            }
+        }
+        if (edges) {
+            float* o = edges + 6 * (size_t(kMaxClusterSize) * x + j);
+            o[0] = a0.w, o[1] = a1.x, o[2] = a1.y, o[3] = a1.z, o[4] = a1.w, o[5] = a2.x;
+        }
         return;
     }
 }
@@ -464,13 +553,27 @@ extern "C" int atr_render_reads_pads(const atr::RenderParams& P, int sched) {
     return prim && !P.sample_sum && (sched == SCHED_HYBRID || sched == SCHED_FLAT);
 }
 
-// Fill rows [0, nrows) of a table of box growths for the scene's `stride` clusters (camera_pads_kernel).
+// Fill rows [0, nrows) of a table of box growths for the scene's `stride` clusters.
+// fold: the loose growths folded with the cameras' det floors (camera_fold_kernel); 0: today's pairs
+// (camera_pads_kernel). wide: a COUNT launch's table, two pairs per cluster (cluster.h pads_entry).
+// info, boxes, edges: atr_camera_pads_row's side outputs of a one-row table (camera_fold_kernel; null
+// otherwise).
 extern "C" hipError_t atr_launch_camera_pads(const atr::DScene* scene, const atr::PadEyes& eyes, int32_t nrows,
-                                             int32_t stride, atr::float2_t* table, hipStream_t s) {
+                                             int32_t stride, int fold, int wide, atr::float2_t* table,
+                                             atr::float2_t* info, atr::float4_t* boxes, float* edges, hipStream_t s) {
+    using namespace atr;
     if (nrows <= 0 || stride <= 0) return hipSuccess;
-    if (nrows > atr::kMaxFrameCams) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(atr::camera_pads_kernel, dim3(unsigned((stride + 255) / 256), unsigned(nrows)), dim3(256), 0, s,
-                       scene, eyes, stride, table);
+    if (nrows > kMaxFrameCams) return hipErrorInvalidValue;
+    const bool side = info || boxes || edges;
+    if (side && nrows != 1) return hipErrorInvalidValue;
+    const dim3 gf(unsigned((stride + 15) / 16)), gp(unsigned((stride + 255) / 256), unsigned(nrows));
+    if (fold || side) {
+        if (wide) hipLaunchKernelGGL(camera_fold_kernel<true>, gf, dim3(256), 0, s, scene, eyes, nrows, stride, fold, table, info, boxes, edges);
+        else hipLaunchKernelGGL(camera_fold_kernel<false>, gf, dim3(256), 0, s, scene, eyes, nrows, stride, fold, table, info, boxes, edges);
+    } else {
+        if (wide) hipLaunchKernelGGL(camera_pads_kernel<true>, gp, dim3(256), 0, s, scene, eyes, stride, table);
+        else hipLaunchKernelGGL(camera_pads_kernel<false>, gp, dim3(256), 0, s, scene, eyes, stride, table);
+    }
     return hipGetLastError();
 }
 

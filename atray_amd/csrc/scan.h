@@ -545,7 +545,9 @@ __device__ __forceinline__ void flat_leaf_step(const Ray& r, const DModel& m, in
                     const uint32_t c = (hi_half ? cfb : cfa) + i;
                     const float4_t lo = m.clus[kClusterBlock * size_t(c)], hi = m.clus[kClusterBlock * size_t(c) + 1];
                     float gl;
-                    if constexpr (PADS) gl = pads[c].x;
+                    // (the COUNT build's table entry starts with the unfolded pair: its cull counters are
+                    // the inline kernels')
+                    if constexpr (PADS) gl = pads[pads_entry<COUNT>(c)].x;
                     else gl = cluster_grow(r.o, lo, hi).x;
                     keep = cluster_hull_keep(r.o, hl, lo, hi, gl);
                 }
@@ -741,7 +743,7 @@ __device__ __forceinline__ SceneHit intersect_models(const DScene* __restrict__ 
                 else h.t = kMaxFloat;
             } else {
                 const float2_t* mp = pads;  // the row's entries of this model
-                if constexpr (F::PADS) mp = pads + __builtin_amdgcn_readfirstlane(m.cl_base);
+                if constexpr (F::PADS) mp = pads + pads_entry<COUNT>(__builtin_amdgcn_readfirstlane(m.cl_base));
                 const int w = threadIdx.x >> 6, ln = threadIdx.x & 63;
                 ATR_PCLK(uint64_t tcs = clock64());
                 flat_query<F, COUNT, KB>(r, m, active, w, ln, err, ct, hyb_a, hyb_b, mp, wcull);

@@ -34,6 +34,9 @@ struct Ctr {
     // hull (counted by lane 0), wave-level iterations of the lane-private cluster loop, cluster
     // tests run (lane level)
     uint32_t culled = 0, lp_wave = 0, ctest = 0;
+    // the facing fold (atr_render_fold_counters): (ray, cluster) pairs that pass the unfolded loose
+    // box and fail the table's folded one, and the primitives screened for them
+    uint32_t fold_box = 0, fold_screen = 0;
 };
 
 // 1 in the lowest active lane of the wavefront (counts a divergent loop's wave-level iterations)

@@ -151,6 +151,7 @@ EXPORTS = [
     "atr_render_start_adaptive", "atr_render_adaptive_info", "atr_render_cull_counters",
     "atr_trace_rays", "atr_occluded_rays", "atr_gather_occlusion", "atr_gather_directions",
     "atr_radiance_rays", "atr_gather_radiance", "atr_mesh_texels", "atr_texels_to_image",
+    "atr_render_fold_counters", "atr_camera_pads_row",
 ]
 # the diagnostic build's extra symbols (include/atray_diag.h; make -C atray_amd/csrc DIAG=1)
 DIAG_EXPORTS = ["atr_render_wave_trace", "atr_render_phase_clocks", "atr_render_path_counters",
@@ -218,6 +219,8 @@ def lib():
         "atr_render_packed_size": ([vp, i32], i64),
         "atr_render_counters": ([vp, P(atr_camera), vp, i32, C.c_uint64, i32, i64 * 10], C.c_int),
         "atr_render_cull_counters": ([vp, P(atr_camera), vp, i32, C.c_uint64, i32, i64 * 5], C.c_int),
+        "atr_render_fold_counters": ([vp, P(atr_camera), vp, i32, C.c_uint64, i32, i64 * 2], C.c_int),
+        "atr_camera_pads_row": ([vp, C.c_float * 3, vp, vp, vp, i64], i64),
         "atr_render_tile_costs": ([vp, P(atr_camera), vp, i32, C.c_uint64, vp], C.c_int),
         "atr_render_wave_trace": ([vp, P(atr_camera), vp, i32, C.c_uint64, i32, vp, i64, P(i64)], C.c_int),
         "atr_packed_pixel_map": ([vp, i32, i32, i32, vp, i64], i64),
@@ -1042,6 +1045,31 @@ class Engine:
         check(lib().atr_render_cull_counters(self.h, C.byref(cam), C.cast(arr, C.c_void_p), n,
                                              C.c_uint64(seed & (2**64 - 1)), int(variant), out), "cull counters")
         return dict(zip(["culled", "lane_private_iters", "dealt_rounds", "dealt_items", "cluster_tests"], [int(x) for x in out]))
+
+    def fold_counters(self, cam, tiles, seed, variant=ATR_KERNEL_AUTO):
+        """What the facing fold removes from the primary kernels' work, counted by one instrumented render
+        (atr_render_fold_counters): (ray, cluster) pairs past the loose box, primitives screened for them."""
+        arr, n = tiles if isinstance(tiles, tuple) else tiles_array(tiles)
+        out = (C.c_int64 * 2)()
+        check(lib().atr_render_fold_counters(self.h, C.byref(cam), C.cast(arr, C.c_void_p), n,
+                                             C.c_uint64(seed & (2**64 - 1)), int(variant), out), "fold counters")
+        return {"loose_passes_removed": int(out[0]), "screened_removed": int(out[1])}
+
+    def camera_pads_row(self, eye):
+        """The row of the table of box growths that a one-camera launch at `eye` reads, built by the launch's
+        own table kernel (atr_camera_pads_row), per scene cluster: row (n, 4) f32 = the entry's loose growth
+        (folded) and tight growth, then the det floor and bits(mask of the primitives treated as
+        rejected); boxes (n, 12) f32 = lo.xyz, P, hi.xyz, q, unfolded loose growth, 0, 0, 0;
+        edges (n, 16, 6) f32 = ab, ac of the cluster's primitive slots (0 past its count)."""
+        e = (C.c_float * 3)(*[float(x) for x in eye])
+        n = int(lib().atr_camera_pads_row(self.h, e, None, None, None, 0))
+        check(min(n, 0), "camera pads row")
+        row, boxes = np.zeros((n, 4), np.float32), np.zeros((n, 12), np.float32)
+        edges = np.zeros((n, 16, 6), np.float32)
+        if n:
+            check(min(int(lib().atr_camera_pads_row(self.h, e, row.ctypes.data, boxes.ctypes.data,
+                                                    edges.ctypes.data, n)), 0), "camera pads row")
+        return row, boxes, edges
 
     def tile_costs(self, cam, tiles, seed):
         """Shader clocks spent per tile by one render of `tiles` (load-balance calibration)."""

@@ -158,7 +158,9 @@ typedef struct atr_ctx atr_ctx;
    primary-only kernels compute each cluster's box growths per ray instead of reading them from the
    per-camera table; unset or any other value: the table. Same output bits either way.
    And a second one: ATR_WAVE_CULL=0 makes them test every cluster of a leaf per ray instead of
-   first culling the leaf's clusters against the wave's direction hull; same bits. */
+   first culling the leaf's clusters against the wave's direction hull; same bits.
+   And a third: ATR_FACING_FOLD=0 leaves the table's loose growths unfolded, sized for the smallest
+   det the culled test accepts instead of the camera's det floor per cluster; same bits. */
 int atr_create(int device, atr_ctx** out);
 int atr_destroy(atr_ctx* ctx);
 const char* atr_version(void);
@@ -375,6 +377,24 @@ int atr_render_counters(atr_ctx* ctx, const atr_camera* cam, const atr_tile* til
    [4] the per-ray cluster tests run ([8] of atr_render_counters less the culled ones). */
 int atr_render_cull_counters(atr_ctx* ctx, const atr_camera* cam, const atr_tile* tiles, int32_t ntiles,
                              uint64_t seed, int32_t variant, int64_t counters_out[5]);
+/* Diagnostic, synchronous: the same instrumented render's counters of the facing fold (DESIGN.md
+   §4b), the work that the folded table takes from the primary kernels: [0] (ray, cluster) pairs that
+   pass the unfolded loose box and fail the folded one, [1] the primitives that were screened for
+   them. Both 0 with ATR_FACING_FOLD=0 or ATR_CAMERA_PADS=0 and for every kernel without the table. */
+int atr_render_fold_counters(atr_ctx* ctx, const atr_camera* cam, const atr_tile* tiles, int32_t ntiles,
+                             uint64_t seed, int32_t variant, int64_t counters_out[2]);
+/* Diagnostic, synchronous: the row of the table of box growths that a one-camera launch of this
+   context at `eye` reads, built as the launch builds it: the same table kernel with the same
+   arguments (with ATR_FACING_FOLD=0 the kernel that fills the unfolded table). Returns the scene's
+   cluster count n (or an error < 0); with row == NULL or cap < n nothing else is done. Every index in
+   [0, n) is a cluster of one of the scene's tree models. row: 4 f32 per cluster = the table's entry
+   {loose growth (folded), tight growth}, then {det floor delta, bits(mask of the primitive slots
+   treated as rejected for every ray)}, side outputs of the folding kernel (with ATR_FACING_FOLD=0 of
+   a second launch of it with the fold switched off: kTol and 0). From the same launch as the second
+   pair: boxes (may be NULL), 12 f32 per cluster = {lo.xyz, P}{hi.xyz, q}{unfolded loose growth, 0,
+   0, 0}; edges (may be NULL), 96 f32 per cluster = ab.xyz, ac.xyz of its 16 primitive slots, 0 past
+   its count. */
+int64_t atr_camera_pads_row(atr_ctx* ctx, const float eye[3], float* row, float* boxes, float* edges, int64_t cap);
 /* Number of pixels a PACKED render of these tiles writes. */
 int64_t atr_render_packed_size(const atr_tile* tiles, int32_t ntiles);
 /* Host-only: pixel index (y * width + x) of every slot of a PACKED render of these tiles, in
