@@ -32,6 +32,7 @@
 
 #include "engine.h"
 #include "host_scene.h"
+#include "refs_budget.h"
 
 namespace atr {
 namespace {
@@ -219,6 +220,7 @@ int build_levels(const HostMesh& m, uint32_t max_faces, hipStream_t s, std::vect
     std::memcpy(nodes[0].hi, box + 3, 12);
     nodes[0].count = nf;
     size_t lvl_begin = 0;
+    uint64_t live = nf;  // primitive references of every leaf so far and of the level in work
     DevBuf d_seg, d_out, d_counts, d_dst;
     size_t seg_cap = 0, ch_cap = 0;
     for (uint32_t level = 0;; ++level) {
@@ -291,6 +293,11 @@ int build_levels(const HostMesh& m, uint32_t max_faces, hipStream_t s, std::vect
             total += counts[b];
         }
         if (total > 0xFFFFFFFFull) return ATR_E_NOMEM;
+        // the host builder's rule (refs_budget.h), from this level's counts and before the next
+        // level's primitive list is allocated or filled
+        for (const uint32_t p : parents) live -= nodes[p].count;
+        live += total;
+        if (live > refs_budget(nf)) return ATR_E_NOMEM;
         lvl.emplace_back();
         BCHK(lvl.back().alloc(size_t(total) * 4));
         BCHK(hipMemcpyAsync(d_dst.p, dst.data(), nch * 4, hipMemcpyHostToDevice, s));

@@ -12,6 +12,7 @@
 #include <fcntl.h>
 #include <unistd.h>
 #include <cerrno>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
@@ -1050,27 +1051,34 @@ hipError_t launch_render(atr_ctx* c, RenderParams& P, int sched, hipStream_t s, 
 
 }  // namespace
 
+// No exception crosses the ABI (atray.h): every entry point that returns a status is a function
+// try block, std::bad_alloc comes back as ATR_E_NOMEM and anything else as ATR_E_INVALID.
+#define ATR_ABI_CATCH                                    \
+    catch (const std::bad_alloc&) { return ATR_E_NOMEM; } \
+    catch (...) { return ATR_E_INVALID; }
+
 extern "C" {
 
 const char* atr_version(void) { return "atray-mi355x 0.2 (gfx950)"; }
 
 // ------------------------------------------------------------------ host prerequisites
-int atr_mesh_parse_obj_threaded(const char* text, size_t len, int32_t threads, atr_mesh** out) {
+int atr_mesh_parse_obj_threaded(const char* text, size_t len, int32_t threads, atr_mesh** out) try {
     if (!text || !out || threads < 0) return ATR_E_INVALID;
     if (threads == 0) threads = default_parse_threads();
-    atr_mesh* m = new (std::nothrow) atr_mesh();
+    std::unique_ptr<atr_mesh> own(new (std::nothrow) atr_mesh());
+    atr_mesh* m = own.get();
     if (!m) return ATR_E_NOMEM;
     const int rc = parse_obj_text(text, len, m->m, threads);
-    if (rc != ATR_OK) { delete m; return rc; }
-    *out = m;
+    if (rc != ATR_OK) return rc;
+    *out = own.release();
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
-int atr_mesh_parse_obj(const char* text, size_t len, atr_mesh** out) {
+int atr_mesh_parse_obj(const char* text, size_t len, atr_mesh** out) try {
     return atr_mesh_parse_obj_threaded(text, len, 1, out);
-}
+} ATR_ABI_CATCH
 
-int atr_mesh_load_obj_threaded(const char* path, int32_t threads, atr_mesh** out) {
+int atr_mesh_load_obj_threaded(const char* path, int32_t threads, atr_mesh** out) try {
     if (!path || !out || threads < 0) return ATR_E_INVALID;
     FILE* f = std::fopen(path, "rb");
     if (!f) return ATR_E_IO;
@@ -1087,16 +1095,17 @@ int atr_mesh_load_obj_threaded(const char* path, int32_t threads, atr_mesh** out
     std::fclose(f);
     if (bad) return ATR_E_IO;
     return atr_mesh_parse_obj_threaded(buf.data(), buf.size(), threads, out);
-}
+} ATR_ABI_CATCH
 
 int atr_mesh_load_obj(const char* path, atr_mesh** out) { return atr_mesh_load_obj_threaded(path, 0, out); }
 
 int atr_mesh_from_arrays(const float* vertices, uint32_t nvertices, const int32_t* face_vertices,
                          uint32_t nfaces, const float* normals, uint32_t nnormals,
-                         const int32_t* face_normals, atr_mesh** out) {
+                         const int32_t* face_normals, atr_mesh** out) try {
     if (!out || (nvertices && !vertices) || (nfaces && !face_vertices)) return ATR_E_INVALID;
     if (nnormals && (!normals || !face_normals)) return ATR_E_INVALID;
-    atr_mesh* m = new (std::nothrow) atr_mesh();
+    std::unique_ptr<atr_mesh> own(new (std::nothrow) atr_mesh());
+    atr_mesh* m = own.get();
     if (!m) return ATR_E_NOMEM;
     for (uint32_t i = 0; i < nvertices; ++i) m->m.vertices.push_back(mk(vertices[3 * i], vertices[3 * i + 1], vertices[3 * i + 2]));
     for (uint32_t i = 0; i < nnormals; ++i) m->m.normals.push_back(mk(normals[3 * i], normals[3 * i + 1], normals[3 * i + 2]));
@@ -1104,22 +1113,22 @@ int atr_mesh_from_arrays(const float* vertices, uint32_t nvertices, const int32_
     m->m.face_t.assign(3 * size_t(nfaces), -1);
     if (nnormals) m->m.face_n.assign(face_normals, face_normals + 3 * size_t(nfaces));
     else m->m.face_n.assign(3 * size_t(nfaces), -1);
-    *out = m;
+    *out = own.release();
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
 void atr_mesh_free(atr_mesh* m) { delete m; }
 
-int atr_mesh_info(const atr_mesh* m, uint32_t* nv, uint32_t* nn, uint32_t* nf) {
+int atr_mesh_info(const atr_mesh* m, uint32_t* nv, uint32_t* nn, uint32_t* nf) try {
     if (!m) return ATR_E_INVALID;
     if (nv) *nv = uint32_t(m->m.vertices.size());
     if (nn) *nn = uint32_t(m->m.normals.size());
     if (nf) *nf = uint32_t(m->m.nfaces());
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
 int atr_mesh_export(const atr_mesh* m, float* vertices, float* normals, float* texcoords, uint32_t* ntexcoords,
-                    int32_t* face_v, int32_t* face_t, int32_t* face_n) {
+                    int32_t* face_v, int32_t* face_t, int32_t* face_n) try {
     if (!m) return ATR_E_INVALID;
     auto put = [](float* dst, const std::vector<V3>& src) {
         if (!dst) return;
@@ -1133,47 +1142,50 @@ int atr_mesh_export(const atr_mesh* m, float* vertices, float* normals, float* t
     if (face_t) std::memcpy(face_t, m->m.face_t.data(), m->m.face_t.size() * sizeof(int32_t));
     if (face_n) std::memcpy(face_n, m->m.face_n.data(), m->m.face_n.size() * sizeof(int32_t));
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
-int atr_mesh_aabb(const atr_mesh* m, float aabb_out[6]) {
+int atr_mesh_aabb(const atr_mesh* m, float aabb_out[6]) try {
     if (!m || !aabb_out) return ATR_E_INVALID;
     mesh_aabb(m->m, aabb_out);
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
-int atr_mesh_translate_to(atr_mesh* m, float aabb[6], atr_vec3 c) {
+int atr_mesh_translate_to(atr_mesh* m, float aabb[6], atr_vec3 c) try {
     if (!m || !aabb) return ATR_E_INVALID;
     mesh_translate(m->m, aabb, mk(c.x, c.y, c.z));
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
-int atr_octree_build(const atr_mesh* m, uint32_t max_faces, atr_octree** out) {
+int atr_octree_build(const atr_mesh* m, uint32_t max_faces, atr_octree** out) try {
     if (!m || !out) return ATR_E_INVALID;
-    atr_octree* t = new (std::nothrow) atr_octree();
+    std::unique_ptr<atr_octree> own(new (std::nothrow) atr_octree());
+    atr_octree* t = own.get();
     if (!t) return ATR_E_NOMEM;
     const int rc = octree_build(m->m, max_faces, t->t);
-    if (rc != ATR_OK) { delete t; return rc; }
-    *out = t;
+    if (rc != ATR_OK) return rc;
+    *out = own.release();
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
 int atr_octree_build_device(const atr_mesh* m, uint32_t max_faces, int32_t device, atr_octree** out,
-                            float ms_out[2]) {
+                            float ms_out[2]) try {
     if (!m || !out || device < 0) return ATR_E_INVALID;
-    atr_octree* t = new (std::nothrow) atr_octree();
+    std::unique_ptr<atr_octree> own(new (std::nothrow) atr_octree());
+    atr_octree* t = own.get();
     if (!t) return ATR_E_NOMEM;
     const int rc = octree_build_device(m->m, max_faces, device, t->t, ms_out);
-    if (rc != ATR_OK) { delete t; return rc; }
-    *out = t;
+    if (rc != ATR_OK) return rc;
+    *out = own.release();
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
 int atr_octree_from_nodes(int32_t nnodes, const float* bounds, const int32_t* children,
                           const uint32_t* leaf_first, const uint32_t* leaf_count, uint32_t nprims,
-                          const float* prim_vertices, const uint32_t* prim_face, atr_octree** out) {
+                          const float* prim_vertices, const uint32_t* prim_face, atr_octree** out) try {
     if (nnodes <= 0 || !bounds || !children || !leaf_first || !leaf_count || !out) return ATR_E_INVALID;
     if (nprims && (!prim_vertices || !prim_face)) return ATR_E_INVALID;
-    atr_octree* t = new (std::nothrow) atr_octree();
+    std::unique_ptr<atr_octree> own(new (std::nothrow) atr_octree());
+    atr_octree* t = own.get();
     if (!t) return ATR_E_NOMEM;
     HostTree& T = t->t;
     T.nnodes = nnodes;
@@ -1184,17 +1196,17 @@ int atr_octree_from_nodes(int32_t nnodes, const float* bounds, const int32_t* ch
     T.prim_vertices.assign(prim_vertices, prim_vertices + 9 * size_t(nprims));
     T.prim_face.assign(prim_face, prim_face + nprims);
     for (int32_t i = 0; i < nnodes; ++i)
-        if (children[i] == 0 && uint64_t(leaf_first[i]) + leaf_count[i] > nprims) { delete t; return ATR_E_INVALID; }
+        if (children[i] == 0 && uint64_t(leaf_first[i]) + leaf_count[i] > nprims) return ATR_E_INVALID;
     const int rc = octree_finish(T);
-    if (rc != ATR_OK) { delete t; return rc; }
-    *out = t;
+    if (rc != ATR_OK) return rc;
+    *out = own.release();
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
 void atr_octree_free(atr_octree* t) { delete t; }
 
 int atr_octree_export(const atr_octree* t, float* bounds, int32_t* children, uint32_t* leaf_first,
-                      uint32_t* leaf_count, float* prim_vertices, uint32_t* prim_face) {
+                      uint32_t* leaf_count, float* prim_vertices, uint32_t* prim_face) try {
     if (!t) return ATR_E_INVALID;
     const HostTree& T = t->t;
     if (bounds) std::memcpy(bounds, T.bounds.data(), T.bounds.size() * sizeof(float));
@@ -1204,20 +1216,20 @@ int atr_octree_export(const atr_octree* t, float* bounds, int32_t* children, uin
     if (prim_vertices) std::memcpy(prim_vertices, T.prim_vertices.data(), T.prim_vertices.size() * sizeof(float));
     if (prim_face) std::memcpy(prim_face, T.prim_face.data(), T.prim_face.size() * sizeof(uint32_t));
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
-int atr_octree_stats(const atr_octree* t, int64_t s[7]) {
+int atr_octree_stats(const atr_octree* t, int64_t s[7]) try {
     if (!t || !s) return ATR_E_INVALID;
     octree_stats(t->t, s);
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
 int atr_camera_set(atr_camera* cm, atr_vec3 eye, atr_vec3 facing, int32_t w, int32_t h, int32_t aa,
-                   uint32_t spp, int32_t bounces, float h_fov) {
+                   uint32_t spp, int32_t bounces, float h_fov) try {
     if (!cm || w <= 0 || h <= 0) return ATR_E_INVALID;
     camera_set(*cm, mk(eye.x, eye.y, eye.z), mk(facing.x, facing.y, facing.z), w, h, aa, spp, bounces, h_fov);
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
 namespace {
 void put_le(uint8_t* p, uint32_t v, int n) {
@@ -1226,7 +1238,7 @@ void put_le(uint8_t* p, uint32_t v, int n) {
 }  // namespace
 
 int atr_write_bmp(const uint32_t* pixels, int32_t width, int32_t height, const char* name, char* out_path,
-                  int32_t out_cap) {
+                  int32_t out_cap) try {
     if (!pixels || !name || width <= 0 || height <= 0) return ATR_E_INVALID;
     const size_t len = std::strlen(name);
     if (len + 8 > 1024) return ATR_E_INVALID;  // the reference's new_name[1024]
@@ -1273,24 +1285,26 @@ int atr_write_bmp(const uint32_t* pixels, int32_t width, int32_t height, const c
         out_path[out_cap - 1] = 0;
     }
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
-int32_t atr_make_tiles(int32_t w, int32_t h, int32_t threads, atr_tile* out, int32_t cap) {
+// The count-returning entry points are guarded too: their results are never negative, so an
+// exception comes back as the negative ATR_E_* code.
+int32_t atr_make_tiles(int32_t w, int32_t h, int32_t threads, atr_tile* out, int32_t cap) try {
     return reference_tiles(w, h, threads, out, out ? cap : 0);
-}
+} ATR_ABI_CATCH
 
 int32_t atr_make_shard_tiles(int32_t w, int32_t h, int32_t side, int32_t rank, int32_t world, atr_tile* out,
-                             int32_t cap) {
+                             int32_t cap) try {
     return shard_tiles(w, h, side, rank, world, out, out ? cap : 0);
-}
+} ATR_ABI_CATCH
 
 int32_t atr_balance_shard_tiles(int32_t w, int32_t h, int32_t side, int32_t world, const int64_t* costs,
-                                int64_t rank0_extra, int32_t* owner_out) {
+                                int64_t rank0_extra, int32_t* owner_out) try {
     return balance_shard_tiles(w, h, side, world, costs, rank0_extra, owner_out);
-}
+} ATR_ABI_CATCH
 
 // ------------------------------------------------------------------ device engine
-int atr_create(int device, atr_ctx** out) {
+int atr_create(int device, atr_ctx** out) try {
     if (!out) return ATR_E_INVALID;
     int n = 0;
     HIPCHK(hipGetDeviceCount(&n));
@@ -1298,6 +1312,8 @@ int atr_create(int device, atr_ctx** out) {
     HIPCHK(hipSetDevice(device));
     atr_ctx* c = new (std::nothrow) atr_ctx();
     if (!c) return ATR_E_NOMEM;
+    // released (atr_destroy: whatever was created so far) on every way out but the last, a throw included
+    struct Owner { atr_ctx* c; ~Owner() { if (c) atr_destroy(c); } } own{c};
     c->device = device;
     // ATR_CAMERA_PADS=0: this context's primary kernels compute the box growths inline (A/B runs and
     // the tests that compare the two); unset or anything else: they read the per-camera table
@@ -1320,19 +1336,17 @@ int atr_create(int device, atr_ctx** out) {
         for (hipEvent_t& e : c->tev) HIPCHK(hipEventCreate(&e));  // timed: a launch's ev_last
         return ATR_OK;
     }();
-    if (rc != ATR_OK) {
-        atr_destroy(c);
-        return rc;
-    }
+    if (rc != ATR_OK) return rc;
+    own.c = nullptr;
     *out = c;
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
 void atr_default_tuning(atr_tuning* out) {
     if (out) *out = default_tuning();
 }
 
-int atr_set_tuning(atr_ctx* c, const atr_tuning* t) {
+int atr_set_tuning(atr_ctx* c, const atr_tuning* t) try {
     if (!c || !t) return ATR_E_INVALID;
     if (t->xcd_chunk < 0 || t->xcd_chunk > 4096 || t->frame_rotate < 0 || t->frame_rotate > 1024 ||
         t->hybrid_a < -4096 || t->hybrid_a > 4096 || t->hybrid_b < -4096 || t->hybrid_b > 4096 ||
@@ -1347,15 +1361,15 @@ int atr_set_tuning(atr_ctx* c, const atr_tuning* t) {
         if (r != 0) return ATR_E_INVALID;
     c->tune = *t;
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
-int atr_get_tuning(atr_ctx* c, atr_tuning* out) {
+int atr_get_tuning(atr_ctx* c, atr_tuning* out) try {
     if (!c || !out) return ATR_E_INVALID;
     *out = c->tune;
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
-int atr_destroy(atr_ctx* c) {
+int atr_destroy(atr_ctx* c) try {
     if (!c) return ATR_E_INVALID;
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
@@ -1405,11 +1419,11 @@ int atr_destroy(atr_ctx* c) {
     if (c->split_fork) (void)hipEventDestroy(c->split_fork);
     delete c;
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
 int atr_scene_upload(atr_ctx* c, const atr_material* mats, int32_t nmats, const atr_model* models,
                      int32_t nmodels, const atr_sphere* spheres, int32_t nspheres, const atr_plane* planes,
-                     int32_t nplanes) {
+                     int32_t nplanes) try {
     if (!c || !mats || nmats <= 0 || nmats > kMaxMaterials || nmodels < 0 || nmodels > kMaxModels ||
         (nmodels && !models) || nspheres < 0 || nplanes < 0 || (nspheres && !spheres) || (nplanes && !planes))
         return ATR_E_INVALID;
@@ -1565,17 +1579,17 @@ int atr_scene_upload(atr_ctx* c, const atr_material* mats, int32_t nmats, const 
     }
     c->nmodels = nmodels;
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
-int atr_scene_info(atr_ctx* c, int64_t* bytes, int32_t* max_nodes, int32_t* max_depth) {
+int atr_scene_info(atr_ctx* c, int64_t* bytes, int32_t* max_nodes, int32_t* max_depth) try {
     if (!c) return ATR_E_INVALID;
     if (bytes) *bytes = c->scene_bytes;
     if (max_nodes) *max_nodes = c->max_nodes;
     if (max_depth) *max_depth = c->max_depth;
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
-int atr_workspace_info(atr_ctx* c, int32_t* workspaces, int64_t* bytes) {
+int atr_workspace_info(atr_ctx* c, int32_t* workspaces, int64_t* bytes) try {
     if (!c) return ATR_E_INVALID;
     int32_t n = 0;
     int64_t b = 0;
@@ -1584,9 +1598,9 @@ int atr_workspace_info(atr_ctx* c, int32_t* workspaces, int64_t* bytes) {
     if (workspaces) *workspaces = n;
     if (bytes) *bytes = b;
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
-int64_t atr_render_packed_size(const atr_tile* tiles, int32_t ntiles) {
+int64_t atr_render_packed_size(const atr_tile* tiles, int32_t ntiles) try {
     if (!tiles || ntiles <= 0) return 0;
     int32_t W = 0, H = 0;
     for (int32_t i = 0; i < ntiles; ++i) {
@@ -1597,10 +1611,10 @@ int64_t atr_render_packed_size(const atr_tile* tiles, int32_t ntiles) {
     int64_t n = 0;
     build_blocks(tiles, ntiles, W, H, b, n);
     return n;
-}
+} ATR_ABI_CATCH
 
 int64_t atr_packed_pixel_map(const atr_tile* tiles, int32_t ntiles, int32_t W, int32_t H, int64_t* out,
-                             int64_t cap) {
+                             int64_t cap) try {
     if (ntiles < 0 || (ntiles && !tiles) || W <= 0 || H <= 0) return ATR_E_INVALID;
     std::vector<DBlock> b;
     int64_t n = 0;
@@ -1617,10 +1631,10 @@ int64_t atr_packed_pixel_map(const atr_tile* tiles, int32_t ntiles, int32_t W, i
         }
     }
     return n;
-}
+} ATR_ABI_CATCH
 
 int atr_render_start_ex(atr_ctx* c, const atr_camera* cam, const atr_tile* tiles, int32_t ntiles,
-                        const atr_frame* fr, uint64_t seed, void* stream, int32_t variant) {
+                        const atr_frame* fr, uint64_t seed, void* stream, int32_t variant) try {
     if (!c || !cam || !fr || !fr->framebuffer || ntiles < 0 || (ntiles && !tiles)) return ATR_E_INVALID;
     if (cam->width <= 0 || cam->height <= 0 || cam->width > (1 << 16) || cam->height > (1 << 16)) return ATR_E_INVALID;
     if (fr->layout != ATR_LAYOUT_IMAGE && fr->layout != ATR_LAYOUT_PACKED) return ATR_E_INVALID;
@@ -1657,7 +1671,7 @@ int atr_render_start_ex(atr_ctx* c, const atr_camera* cam, const atr_tile* tiles
     c->last_stream = s;
     c->last_ntiles = ntiles;
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
 // One sample pass of a frame (atray.h): samples [first_sample, first_sample + spp) of every pixel,
 // continuing the running sums in sample_sum. PATHS (the camera kernel's ACCUM flavour and
@@ -1666,7 +1680,7 @@ int atr_render_start_ex(atr_ctx* c, const atr_camera* cam, const atr_tile* tiles
 // a fraction of a frame, and its cost would train the plan of the tile list's full frames.
 int atr_render_start_samples(atr_ctx* c, const atr_camera* cam, const atr_tile* tiles, int32_t ntiles,
                              const atr_frame* fr, uint64_t seed, void* stream, int32_t variant,
-                             uint32_t first_sample, float* sample_sum) {
+                             uint32_t first_sample, float* sample_sum) try {
     if (!c || !cam || !fr || !fr->framebuffer || ntiles < 0 || (ntiles && !tiles)) return ATR_E_INVALID;
     if (cam->width <= 0 || cam->height <= 0 || cam->width > (1 << 16) || cam->height > (1 << 16)) return ATR_E_INVALID;
     if (fr->layout != ATR_LAYOUT_IMAGE && fr->layout != ATR_LAYOUT_PACKED) return ATR_E_INVALID;
@@ -1712,14 +1726,14 @@ int atr_render_start_samples(atr_ctx* c, const atr_camera* cam, const atr_tile* 
     c->last_stream = s;
     c->last_ntiles = ntiles;
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
 // One adaptive sample pass (atray.h): atr_render_start_samples' PATHS route with a
 // device-side live list, so only the pixels whose count equals first_sample are traced and
 // resolved. The pass's counts go to a slot of the context's info ring, zeroed on the stream first.
 int atr_render_start_adaptive(atr_ctx* c, const atr_camera* cam, const atr_tile* tiles, int32_t ntiles,
                               const atr_frame* fr, uint64_t seed, void* stream, int32_t variant,
-                              uint32_t first_sample, float* sample_sum, uint32_t* sample_count, float tolerance) {
+                              uint32_t first_sample, float* sample_sum, uint32_t* sample_count, float tolerance) try {
     if (!c || !cam || !fr || !fr->framebuffer || ntiles < 0 || (ntiles && !tiles)) return ATR_E_INVALID;
     if (cam->width <= 0 || cam->height <= 0 || cam->width > (1 << 16) || cam->height > (1 << 16)) return ATR_E_INVALID;
     if (fr->layout != ATR_LAYOUT_IMAGE && fr->layout != ATR_LAYOUT_PACKED) return ATR_E_INVALID;
@@ -1775,7 +1789,7 @@ int atr_render_start_adaptive(atr_ctx* c, const atr_camera* cam, const atr_tile*
     c->last_stream = s;
     c->last_ntiles = ntiles;
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
 // A batch of the caller's rays (atray.h): with an order, the batch's keys, the bin
 // scan and the key order (query.hip, paths.hip); then the persistent query launch. The traced rays
@@ -1869,7 +1883,7 @@ int query_call(atr_ctx* c, const float* origins, const float* directions, int64_
 }  // extern "C++"
 
 int atr_trace_rays(atr_ctx* c, const float* origins, const float* directions, int64_t nrays, const atr_ray_hits* hits,
-                   int32_t variant, int32_t sort_bits, void* stream) {
+                   int32_t variant, int32_t sort_bits, void* stream) try {
     const int rc = query_args(c, origins, directions, nrays, hits, variant, sort_bits);
     if (rc != ATR_OK || nrays == 0) return rc;
     return query_call(c, origins, directions, nrays, sort_bits, stream, hits->traced_rays,
@@ -1883,12 +1897,12 @@ int atr_trace_rays(atr_ctx* c, const float* origins, const float* directions, in
                           Q.normal = hits->normal;
                           return atr_launch_query(Q, variant == ATR_KERNEL_LANE ? 1 : 0, c->ncu, s);
                       });
-}
+} ATR_ABI_CATCH
 
 // An occlusion query (atray.h): the ray query's order and workspace, its own kernel.
 int atr_occluded_rays(atr_ctx* c, const float* origins, const float* directions, const float* t_max, int64_t nrays,
                       uint8_t* occluded, unsigned long long* traced_rays, int32_t variant, int32_t sort_bits,
-                      void* stream) {
+                      void* stream) try {
     const int rc = query_args(c, origins, directions, nrays, occluded, variant, sort_bits);
     if (rc != ATR_OK || nrays == 0) return rc;
     return query_call(c, origins, directions, nrays, sort_bits, stream, traced_rays,
@@ -1907,14 +1921,14 @@ int atr_occluded_rays(atr_ctx* c, const float* origins, const float* directions,
                           P.perm = Q.sort.bits > 0 ? Q.sort.perm : nullptr;
                           return atr_launch_occlusion(P, variant == ATR_KERNEL_LANE ? 1 : 0, c->ncu, s);
                       });
-}
+} ATR_ABI_CATCH
 
 // A hemisphere gather (atray.h): the queries' claim counter, ring set and hand-over
 // between streams (query_call without an order), its own kernel; the per-point outputs are zeroed on
 // the stream first, inside the timed range.
 int atr_gather_occlusion(atr_ctx* c, const float* points, const float* normals, const float* t_max, int64_t npoints,
                          int32_t nsamples, uint32_t first_sample, int64_t point_base, uint64_t seed,
-                         const atr_gather_out* out, int32_t variant, void* stream) {
+                         const atr_gather_out* out, int32_t variant, void* stream) try {
     if (!c) return ATR_E_INVALID;
     if (npoints < 0 || nsamples < 1 || nsamples > 65536) return ATR_E_INVALID;
     if (uint64_t(first_sample) + uint64_t(nsamples) > (uint64_t(1) << 24)) return ATR_E_INVALID;
@@ -1953,12 +1967,12 @@ int atr_gather_occlusion(atr_ctx* c, const float* points, const float* normals, 
                           if (P.mask && (e = hipMemsetAsync(P.mask, 0, per * words, s)) != hipSuccess) return e;
                           return atr_launch_gather(P, variant == ATR_KERNEL_LANE ? 1 : 0, c->ncu, s);
                       });
-}
+} ATR_ABI_CATCH
 
 // The gather's sampler on the host (atray.h): the kernel's own functions (engine.h), compiled with the
 // library's -ffp-contract=off. No device, no context.
 int atr_gather_directions(const float* normals, int64_t npoints, int32_t nsamples, uint32_t first_sample,
-                          int64_t point_base, uint64_t seed, float* dirs_out, uint8_t* traced_out) {
+                          int64_t point_base, uint64_t seed, float* dirs_out, uint8_t* traced_out) try {
     if (npoints < 0 || nsamples < 1 || nsamples > 65536) return ATR_E_INVALID;
     if (uint64_t(first_sample) + uint64_t(nsamples) > (uint64_t(1) << 24)) return ATR_E_INVALID;
     if (point_base < 0 || npoints > (int64_t(1) << 39) || point_base > (int64_t(1) << 39) - npoints) return ATR_E_INVALID;
@@ -1985,7 +1999,7 @@ int atr_gather_directions(const float* normals, int64_t npoints, int32_t nsample
         }
     }
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
 // Path-traced radiance along the caller's rays (atray.h): the path engine on a path
 // workspace, batched over groups of 64 rays the way launch_paths_range batches over cells, with the
@@ -1995,7 +2009,7 @@ int atr_gather_directions(const float* normals, int64_t npoints, int32_t nsample
 // set of the ring, as a render's and a query's do.
 int atr_radiance_rays(atr_ctx* c, const float* origins, const float* directions, int64_t nrays, int32_t nsamples,
                       uint32_t first_sample, int64_t ray_base, int32_t bounce_limit, uint64_t seed,
-                      const atr_radiance_out* out, int32_t sort_bits, void* stream) {
+                      const atr_radiance_out* out, int32_t sort_bits, void* stream) try {
     if (!c) return ATR_E_INVALID;
     if (nrays < 0 || nrays >= (int64_t(1) << 31) || nsamples < 1 || nsamples > 65536) return ATR_E_INVALID;
     // the stream hash shifts the sample index by 40 bits, and float(total) is exact up to 2^24
@@ -2081,7 +2095,7 @@ int atr_radiance_rays(atr_ctx* c, const float* origins, const float* directions,
     c->last_stream = s;
     c->last_ntiles = 0;
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
 // Hemisphere radiance gathered on the device (atray.h): atr_radiance_rays' flow with the
 // point as the unit of batching -- a batch is a whole number of points (at least one, even when
@@ -2091,7 +2105,7 @@ int atr_radiance_rays(atr_ctx* c, const float* origins, const float* directions,
 // is enqueued and there is no cell-kernel fallback.
 int atr_gather_radiance(atr_ctx* c, const float* points, const float* normals, int64_t npoints, int32_t nsamples,
                         uint32_t first_sample, int64_t point_base, int32_t bounce_limit, uint64_t seed,
-                        const atr_gather_radiance_out* out, int32_t sort_bits, void* stream) {
+                        const atr_gather_radiance_out* out, int32_t sort_bits, void* stream) try {
     if (!c) return ATR_E_INVALID;
     if (npoints < 0 || npoints >= (int64_t(1) << 31) || nsamples < 1 || nsamples > 65536) return ATR_E_INVALID;
     if (npoints * int64_t(nsamples) >= (int64_t(1) << 31)) return ATR_E_INVALID;
@@ -2182,9 +2196,9 @@ int atr_gather_radiance(atr_ctx* c, const float* points, const float* normals, i
     c->last_stream = s;
     c->last_ntiles = 0;
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
-int atr_render_adaptive_info(atr_ctx* c, int64_t info_out[4]) {
+int atr_render_adaptive_info(atr_ctx* c, int64_t info_out[4]) try {
     if (!c || !info_out || c->adapt_last < 0) return ATR_E_INVALID;
     HIPCHK(hipSetDevice(c->device));
     unsigned long long v[4];
@@ -2194,7 +2208,7 @@ int atr_render_adaptive_info(atr_ctx* c, int64_t info_out[4]) {
     info_out[2] = int64_t(v[2]);
     info_out[3] = int64_t(v[0]) - int64_t(v[3]);  // live at the start minus the newly converged
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
 namespace {
 // Frames in flight in one launch (atr_render_start_frames / _cameras): ncams == 1 -> every frame
@@ -2270,19 +2284,19 @@ int start_frames(atr_ctx* c, const atr_camera* cams, int32_t ncams, const atr_ti
 
 int atr_render_start_frames(atr_ctx* c, const atr_camera* cam, const atr_tile* tiles, int32_t ntiles,
                             const atr_frame* fr, int32_t nframes, int64_t frame_stride, uint64_t seed, void* stream,
-                            int32_t variant) {
+                            int32_t variant) try {
     return start_frames(c, cam, 1, tiles, ntiles, fr, nframes, frame_stride, seed, stream, variant);
-}
+} ATR_ABI_CATCH
 
 int atr_render_start_cameras(atr_ctx* c, const atr_camera* cams, int32_t nframes, const atr_tile* tiles,
                              int32_t ntiles, const atr_frame* fr, int64_t frame_stride, uint64_t seed, void* stream,
-                             int32_t variant) {
+                             int32_t variant) try {
     return start_frames(c, cams, nframes, tiles, ntiles, fr, nframes, frame_stride, seed, stream, variant);
-}
+} ATR_ABI_CATCH
 
 #ifdef ATR_DIAG
 int atr_render_wave_trace(atr_ctx* c, const atr_camera* cam, const atr_tile* tiles, int32_t ntiles,
-                          uint64_t seed, int32_t variant, uint64_t* out, int64_t cap, int64_t* nblocks) {
+                          uint64_t seed, int32_t variant, uint64_t* out, int64_t cap, int64_t* nblocks) try {
     if (!c || !cam || !nblocks || ntiles < 0 || (ntiles && !tiles)) return ATR_E_INVALID;
     if (!c->d_scene) return ATR_E_NOSCENE;
     HIPCHK(hipSetDevice(c->device));
@@ -2313,7 +2327,7 @@ int atr_render_wave_trace(atr_ctx* c, const atr_camera* cam, const atr_tile* til
     HIPCHK(hipDeviceSynchronize());
     if (nb) HIPCHK(hipMemcpy(out, tr.p, 3 * nb * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
 #endif  // ATR_DIAG
 
@@ -2354,17 +2368,17 @@ static int count_launch(atr_ctx* c, const atr_camera* cam, const atr_tile* tiles
 }
 
 int atr_render_counters(atr_ctx* c, const atr_camera* cam, const atr_tile* tiles, int32_t ntiles,
-                        uint64_t seed, int32_t variant, int64_t out[10]) {
+                        uint64_t seed, int32_t variant, int64_t out[10]) try {
     if (!out) return ATR_E_INVALID;
     unsigned long long h[kCounterSlots];
     const int rc = count_launch(c, cam, tiles, ntiles, seed, variant, h);
     if (rc != ATR_OK) return rc;
     for (int k = 0; k < 10; ++k) out[k] = int64_t(h[k]);
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
 int atr_render_cull_counters(atr_ctx* c, const atr_camera* cam, const atr_tile* tiles, int32_t ntiles,
-                             uint64_t seed, int32_t variant, int64_t out[5]) {
+                             uint64_t seed, int32_t variant, int64_t out[5]) try {
     if (!out) return ATR_E_INVALID;
     unsigned long long h[kCounterSlots];
     const int rc = count_launch(c, cam, tiles, ntiles, seed, variant, h);
@@ -2375,10 +2389,10 @@ int atr_render_cull_counters(atr_ctx* c, const atr_camera* cam, const atr_tile* 
     out[2] = int64_t(h[25]);  // dealt rounds
     out[3] = int64_t(h[26]);  // dealt items
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
 int atr_render_fold_counters(atr_ctx* c, const atr_camera* cam, const atr_tile* tiles, int32_t ntiles,
-                             uint64_t seed, int32_t variant, int64_t out[2]) {
+                             uint64_t seed, int32_t variant, int64_t out[2]) try {
     if (!out) return ATR_E_INVALID;
     unsigned long long h[kCounterSlots];
     const int rc = count_launch(c, cam, tiles, ntiles, seed, variant, h);
@@ -2386,9 +2400,9 @@ int atr_render_fold_counters(atr_ctx* c, const atr_camera* cam, const atr_tile* 
     out[0] = int64_t(h[30]);  // (ray, cluster) pairs past the unfolded loose box that fail the folded one
     out[1] = int64_t(h[31]);  // the primitives screened for them
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
-int64_t atr_camera_pads_row(atr_ctx* c, const float eye[3], float* row, float* boxes, float* edges, int64_t cap) {
+int64_t atr_camera_pads_row(atr_ctx* c, const float eye[3], float* row, float* boxes, float* edges, int64_t cap) try {
     if (!c || !eye || cap < 0) return ATR_E_INVALID;
     if (!c->d_scene) return ATR_E_NOSCENE;
     const int64_t n = c->nclusters;
@@ -2434,31 +2448,31 @@ int64_t atr_camera_pads_row(atr_ctx* c, const float eye[3], float* row, float* b
     if (boxes) HIPCHK(hipMemcpy(boxes, d_box.p, nn * 3 * sizeof(float4_t), hipMemcpyDeviceToHost));
     if (edges) HIPCHK(hipMemcpy(edges, d_edge.p, nn * 96 * sizeof(float), hipMemcpyDeviceToHost));
     return n;
-}
+} ATR_ABI_CATCH
 
 #ifdef ATR_DIAG
 int atr_render_phase_clocks(atr_ctx* c, const atr_camera* cam, const atr_tile* tiles, int32_t ntiles,
-                            uint64_t seed, int32_t variant, int64_t out[6]) {
+                            uint64_t seed, int32_t variant, int64_t out[6]) try {
     if (!out) return ATR_E_INVALID;
     unsigned long long h[kCounterSlots];
     const int rc = count_launch(c, cam, tiles, ntiles, seed, variant, h);
     if (rc != ATR_OK) return rc;
     for (int k = 0; k < 6; ++k) out[k] = int64_t(h[10 + k]);
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
 int atr_render_path_counters(atr_ctx* c, const atr_camera* cam, const atr_tile* tiles, int32_t ntiles,
-                             uint64_t seed, int32_t variant, int64_t out[6]) {
+                             uint64_t seed, int32_t variant, int64_t out[6]) try {
     if (!out) return ATR_E_INVALID;
     unsigned long long h[kCounterSlots];
     const int rc = count_launch(c, cam, tiles, ntiles, seed, variant, h);
     if (rc != ATR_OK) return rc;
     for (int k = 0; k < 6; ++k) out[k] = int64_t(h[16 + k]);
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
 int atr_render_simd_counters(atr_ctx* c, const atr_camera* cam, const atr_tile* tiles, int32_t ntiles,
-                             uint64_t seed, int32_t variant, int64_t out[7]) {
+                             uint64_t seed, int32_t variant, int64_t out[7]) try {
     if (!out) return ATR_E_INVALID;
     unsigned long long h[kCounterSlots];
     const int rc = count_launch(c, cam, tiles, ntiles, seed, variant, h);
@@ -2468,12 +2482,12 @@ int atr_render_simd_counters(atr_ctx* c, const atr_camera* cam, const atr_tile* 
     for (int k = 0; k < 4; ++k) out[2 + k] = int64_t(h[23 + k]);
     out[6] = int64_t(h[0]);   // traced rays
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
 #endif  // ATR_DIAG
 
 int atr_render_tile_costs(atr_ctx* c, const atr_camera* cam, const atr_tile* tiles, int32_t ntiles,
-                          uint64_t seed, int64_t* cost_out) {
+                          uint64_t seed, int64_t* cost_out) try {
     if (!c || !cam || (ntiles && (!tiles || !cost_out)) || ntiles < 0) return ATR_E_INVALID;
     if (!c->d_scene) return ATR_E_NOSCENE;
     HIPCHK(hipSetDevice(c->device));
@@ -2523,11 +2537,11 @@ int atr_render_tile_costs(atr_ctx* c, const atr_camera* cam, const atr_tile* til
         if (o >= 0) cost_out[o] += int64_t(h[k]);
     }
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
 int atr_render_start_progressive(atr_ctx* c, const atr_camera* cam, const atr_tile* tiles, int32_t ntiles,
                                  const atr_frame* fr, uint64_t seed, void* stream, int32_t variant,
-                                 int32_t tiles_per_launch) {
+                                 int32_t tiles_per_launch) try {
     if (!c || !cam || !fr || !fr->framebuffer || ntiles < 0 || (ntiles && !tiles) || tiles_per_launch < 1)
         return ATR_E_INVALID;
     if (cam->width <= 0 || cam->height <= 0 || cam->width > (1 << 16) || cam->height > (1 << 16)) return ATR_E_INVALID;
@@ -2588,12 +2602,12 @@ int atr_render_start_progressive(atr_ctx* c, const atr_camera* cam, const atr_ti
     c->last_stream = s;
     c->last_ntiles = ntiles;
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
 int atr_render_start(atr_ctx* c, const atr_camera* cam, const atr_tile* tiles, int32_t ntiles,
-                     const atr_frame* fr, uint64_t seed, void* stream) {
+                     const atr_frame* fr, uint64_t seed, void* stream) try {
     return atr_render_start_ex(c, cam, tiles, ntiles, fr, seed, stream, ATR_KERNEL_AUTO);
-}
+} ATR_ABI_CATCH
 
 // ------------------------------------------------------------------ lightmap texels (texels.hip)
 namespace {
@@ -2609,7 +2623,7 @@ size_t round_up(size_t n, size_t a) { return (n + a - 1) / a * a; }
 }  // namespace
 
 int atr_mesh_texels(atr_ctx* c, const atr_mesh* mesh, int32_t width, int32_t height, int32_t flags, int64_t cap,
-                    const atr_texels_out* out, int64_t* ncovered, float ms_out[2]) {
+                    const atr_texels_out* out, int64_t* ncovered, float ms_out[2]) try {
     if (!c || !mesh || !out || !ncovered) return ATR_E_INVALID;
     const HostMesh& M = mesh->m;
     const size_t nf = M.nfaces();
@@ -2715,10 +2729,10 @@ int atr_mesh_texels(atr_ctx* c, const atr_mesh* mesh, int32_t width, int32_t hei
         ms_out[1] = dev;
     }
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
 int atr_texels_to_image(atr_ctx* c, const float* values, const int32_t* texel, int64_t ncovered, int32_t width,
-                        int32_t height, int32_t passes, const float fill[3], float* image, void* stream) {
+                        int32_t height, int32_t passes, const float fill[3], float* image, void* stream) try {
     if (!c || !image || !fill) return ATR_E_INVALID;
     if (width < 1 || width > kTexelMaxSide || height < 1 || height > kTexelMaxSide || passes < 0 ||
         passes > kTexelMaxPasses)
@@ -2775,9 +2789,9 @@ int atr_texels_to_image(atr_ctx* c, const float* values, const int32_t* texel, i
     c->last_stream = s;
     c->last_ntiles = 0;
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
-int atr_render_wait(atr_ctx* c, uint32_t timeout_ms, int32_t* tiles_done) {
+int atr_render_wait(atr_ctx* c, uint32_t timeout_ms, int32_t* tiles_done) try {
     if (!c) return ATR_E_INVALID;
     if (tiles_done) *tiles_done = 0;
     if (!c->have_render) { return ATR_OK; }
@@ -2816,17 +2830,17 @@ int atr_render_wait(atr_ctx* c, uint32_t timeout_ms, int32_t* tiles_done) {
     }
     if (tiles_done) *tiles_done = c->last_ntiles;
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
-int atr_last_kernel_ms(atr_ctx* c, float* ms) {
+int atr_last_kernel_ms(atr_ctx* c, float* ms) try {
     if (!c || !ms || !c->have_render) return ATR_E_INVALID;
     HIPCHK(hipEventSynchronize(c->ev_last));
     HIPCHK(hipEventElapsedTime(ms, c->ev_start, c->ev_last));
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
 int atr_unpack(atr_ctx* c, const atr_tile* tiles, int32_t ntiles, int32_t width, const uint32_t* packed,
-               uint32_t* image, void* stream) {
+               uint32_t* image, void* stream) try {
     if (!c || !packed || !image || width <= 0 || ntiles < 0 || (ntiles && !tiles)) return ATR_E_INVALID;
     HIPCHK(hipSetDevice(c->device));
     int32_t H = 0;
@@ -2838,10 +2852,10 @@ int atr_unpack(atr_ctx* c, const atr_tile* tiles, int32_t ntiles, int32_t width,
     HIPCHK(atr_launch_unpack(static_cast<const DBlock*>(bs->dev.p), int32_t(bs->host.size()), width, packed, image, s));
     HIPCHK(note_launch(c, s));
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
 int atr_tile_ray_casts(atr_ctx* c, const atr_tile* tiles, int32_t ntiles, int32_t width,
-                       const uint32_t* casts, int64_t* out, void* stream) {
+                       const uint32_t* casts, int64_t* out, void* stream) try {
     if (!c || !casts || !out || width <= 0 || ntiles < 0 || (ntiles && !tiles)) return ATR_E_INVALID;
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = the null stream (HIP convention)
@@ -2852,11 +2866,11 @@ int atr_tile_ray_casts(atr_ctx* c, const atr_tile* tiles, int32_t ntiles, int32_
     HIPCHK(hipFreeAsync(dt, s));
     HIPCHK(hipStreamSynchronize(s));
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
 int atr_packed_tile_ray_casts(atr_ctx* c, const atr_tile* tiles, int32_t ntiles, int32_t width, int32_t height,
                               const uint32_t* casts, int32_t nframes, int64_t frame_stride, int64_t* out,
-                              void* stream) {
+                              void* stream) try {
     if (!c || !casts || !out || width <= 0 || height <= 0 || ntiles < 0 || (ntiles && !tiles) || nframes < 0 ||
         nframes > 65535)
         return ATR_E_INVALID;
@@ -2903,22 +2917,22 @@ int atr_packed_tile_ray_casts(atr_ctx* c, const atr_tile* tiles, int32_t ntiles,
                                         ntiles, reinterpret_cast<unsigned long long*>(out), s));
     HIPCHK(note_launch(c, s));
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
-int atr_pack_bgr(atr_ctx* c, const uint32_t* framebuffer, int64_t npixels, uint8_t* out, void* stream) {
+int atr_pack_bgr(atr_ctx* c, const uint32_t* framebuffer, int64_t npixels, uint8_t* out, void* stream) try {
     if (!c || npixels < 0 || (npixels && (!framebuffer || !out))) return ATR_E_INVALID;
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(atr_launch_pack_bgr(framebuffer, npixels, out, static_cast<hipStream_t>(stream)));
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
 int atr_scatter_bgr(atr_ctx* c, const uint8_t* packed, int64_t npixels, const int64_t* dst_index, uint32_t* image,
-                    void* stream) {
+                    void* stream) try {
     if (!c || npixels < 0 || (npixels && (!packed || !dst_index || !image))) return ATR_E_INVALID;
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(atr_launch_scatter_bgr(packed, npixels, dst_index, image, static_cast<hipStream_t>(stream)));
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
 int64_t atr_pack_bgr_masked_bound(int64_t npixels) {
     if (npixels < 0) return ATR_E_INVALID;
@@ -2927,25 +2941,25 @@ int64_t atr_pack_bgr_masked_bound(int64_t npixels) {
 }
 
 int atr_pack_bgr_masked(atr_ctx* c, const uint32_t* framebuffer, int64_t npixels, uint32_t background, uint8_t* out,
-                        int64_t* nbytes, void* stream) {
+                        int64_t* nbytes, void* stream) try {
     if (!c || npixels < 0 || npixels >= (int64_t(1) << 32) || !out || !nbytes || (npixels && !framebuffer))
         return ATR_E_INVALID;
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(atr_launch_pack_bgr_masked(framebuffer, npixels, background, out, nbytes, static_cast<hipStream_t>(stream)));
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
 int atr_scatter_bgr_masked(atr_ctx* c, const uint8_t* packed, int64_t npixels, const int64_t* dst_index,
-                           uint32_t* image, void* stream) {
+                           uint32_t* image, void* stream) try {
     if (!c || npixels < 0 || npixels >= (int64_t(1) << 32) || (npixels && (!packed || !dst_index || !image)))
         return ATR_E_INVALID;
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(atr_launch_scatter_bgr_masked(packed, npixels, dst_index, image, static_cast<hipStream_t>(stream)));
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
 int atr_unpack_masked(atr_ctx* c, const atr_tile* tiles, int32_t ntiles, int32_t width, int32_t height,
-                      const uint8_t* packed, int32_t nframes, uint32_t* image, int64_t image_stride, void* stream) {
+                      const uint8_t* packed, int32_t nframes, uint32_t* image, int64_t image_stride, void* stream) try {
     if (!c || !packed || !image || width <= 0 || height <= 0 || ntiles < 0 || (ntiles && !tiles) || nframes < 0 ||
         image_stride < int64_t(width) * height)
         return ATR_E_INVALID;
@@ -2961,11 +2975,11 @@ int atr_unpack_masked(atr_ctx* c, const atr_tile* tiles, int32_t ntiles, int32_t
                                     nframes, own, image, image_stride, s));
     HIPCHK(note_launch(c, s));
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
 int atr_unpack_masked_ranks(atr_ctx* c, int32_t nsrc, const atr_tile* const* tiles, const int32_t* ntiles,
                             int32_t width, int32_t height, const uint8_t* const* packed, const int32_t* raw,
-                            int32_t nframes, uint32_t* image, int64_t image_stride, void* stream) {
+                            int32_t nframes, uint32_t* image, int64_t image_stride, void* stream) try {
     if (!c || nsrc < 0 || (nsrc && (!tiles || !ntiles || !packed)) || !image || width <= 0 || height <= 0 ||
         nframes < 0 || image_stride < int64_t(width) * height)
         return ATR_E_INVALID;
@@ -2998,11 +3012,11 @@ int atr_unpack_masked_ranks(atr_ctx* c, int32_t nsrc, const atr_tile* const* til
         HIPCHK(note_launch(c, s));
     }
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
 int atr_render_plan_info(atr_ctx* c, const atr_tile* tiles, int32_t ntiles, int32_t width, int32_t height,
                          int32_t* base_out, uint32_t* mask_hi_lo_out, int64_t cap, uint64_t* cost_out,
-                         int64_t* nplanned) {
+                         int64_t* nplanned) try {
     if (!c || !nplanned || width <= 0 || height <= 0 || ntiles < 0 || (ntiles && !tiles)) return ATR_E_INVALID;
     HIPCHK(hipSetDevice(c->device));
     int rc = ATR_OK;
@@ -3027,9 +3041,9 @@ int atr_render_plan_info(atr_ctx* c, const atr_tile* tiles, int32_t ntiles, int3
     }
     if (cost_out) HIPCHK(hipMemcpy(cost_out, bs->cost_last.p, size_t(nb) * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
-int atr_set_cell_plan(atr_ctx* c, int32_t width, int32_t height, const uint8_t* plan) {
+int atr_set_cell_plan(atr_ctx* c, int32_t width, int32_t height, const uint8_t* plan) try {
     if (!c || (plan && (width <= 0 || height <= 0))) return ATR_E_INVALID;
     const int32_t cw = (width + 7) / 8, ch = (height + 7) / 8;
     if (plan) {
@@ -3046,9 +3060,9 @@ int atr_set_cell_plan(atr_ctx* c, int32_t width, int32_t height, const uint8_t* 
     }
     ++c->cplan_gen;  // cached block lists are rebuilt on their next use
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
-int atr_render_cell_costs(atr_ctx* c, const atr_camera* cam, uint64_t seed, int32_t variant, int64_t* out) {
+int atr_render_cell_costs(atr_ctx* c, const atr_camera* cam, uint64_t seed, int32_t variant, int64_t* out) try {
     if (!c || !cam || !out || cam->width <= 0 || cam->height <= 0) return ATR_E_INVALID;
     if (!c->d_scene) return ATR_E_NOSCENE;
     HIPCHK(hipSetDevice(c->device));
@@ -3085,39 +3099,39 @@ int atr_render_cell_costs(atr_ctx* c, const atr_camera* cam, uint64_t seed, int3
     for (size_t k = 0; k < nb; ++k)  // a split cell's waves add up
         out[size_t(bs->host[k].y0 / 8) * size_t(cw) + size_t(bs->host[k].x0 / 8)] += int64_t(h[k]);
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
-int atr_device_alloc(atr_ctx* c, size_t bytes, void** p) {
+int atr_device_alloc(atr_ctx* c, size_t bytes, void** p) try {
     if (!c || !p) return ATR_E_INVALID;
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipMalloc(p, bytes ? bytes : 16));
     return ATR_OK;
-}
-int atr_device_free(atr_ctx* c, void* p) {
+} ATR_ABI_CATCH
+int atr_device_free(atr_ctx* c, void* p) try {
     if (!c) return ATR_E_INVALID;
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipFree(p));
     return ATR_OK;
-}
-int atr_memcpy_d2h(atr_ctx* c, void* dst, const void* src, size_t bytes) {
+} ATR_ABI_CATCH
+int atr_memcpy_d2h(atr_ctx* c, void* dst, const void* src, size_t bytes) try {
     if (!c || !dst || !src) return ATR_E_INVALID;
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
     return ATR_OK;
-}
-int atr_memcpy_h2d(atr_ctx* c, void* dst, const void* src, size_t bytes) {
+} ATR_ABI_CATCH
+int atr_memcpy_h2d(atr_ctx* c, void* dst, const void* src, size_t bytes) try {
     if (!c || !dst || !src) return ATR_E_INVALID;
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipDeviceSynchronize());  // a render may still read the destination
     HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
     return ATR_OK;
-}
-int atr_memset_d(atr_ctx* c, void* p, int v, size_t bytes) {
+} ATR_ABI_CATCH
+int atr_memset_d(atr_ctx* c, void* p, int v, size_t bytes) try {
     if (!c || !p) return ATR_E_INVALID;
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipMemset(p, v, bytes));
     return ATR_OK;
-}
+} ATR_ABI_CATCH
 
 }  // extern "C"

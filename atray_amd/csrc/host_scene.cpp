@@ -13,6 +13,7 @@
 
 #include "engine.h"
 #include "host_scene.h"
+#include "refs_budget.h"
 
 using namespace atr;
 
@@ -73,6 +74,10 @@ int atr::octree_build(const HostMesh& m, uint32_t max_faces, HostTree& T) {
             if (f[k] < 0 || size_t(f[k]) >= m.vertices.size()) return ATR_E_INVALID;
         nodes[0].prims[i] = Tri9{m.vertices[f[0]], m.vertices[f[1]], m.vertices[f[2]], uint32_t(i)};
     }
+    // live primitive references: those of every node that is a leaf so far or still on the work
+    // list. A split never lowers the sum; past refs_budget the build is refused (refs_budget.h)
+    const uint64_t budget = refs_budget(nf);
+    uint64_t live = nf;
     std::vector<int32_t> todo{0};
     while (!todo.empty()) {
         const int32_t id = todo.back();
@@ -101,11 +106,16 @@ int atr::octree_build(const HostMesh& m, uint32_t max_faces, HostTree& T) {
             cb[k][2] = zf ? s.z : L[2]; cb[k][5] = zf ? H[2] : s.z;
         }
         std::vector<Tri9> parts[8];
-        for (const Tri9& t : nodes[id].prims)  // vertex-in-box assignment (:10-17, :181-228)
+        live -= nodes[id].prims.size();
+        for (const Tri9& t : nodes[id].prims) {  // vertex-in-box assignment (:10-17, :181-228)
             for (int k = 0; k < 8; ++k)
                 if (pt_in(t.a, cb[k], cb[k] + 3) || pt_in(t.b, cb[k], cb[k] + 3) ||
-                    pt_in(t.c, cb[k], cb[k] + 3))
+                    pt_in(t.c, cb[k], cb[k] + 3)) {
                     parts[k].push_back(t);
+                    ++live;
+                }
+            if (live > budget) return ATR_E_NOMEM;
+        }
         const int32_t first = int32_t(nodes.size());
         const int depth = nodes[id].depth;
         nodes[id].prims.clear();

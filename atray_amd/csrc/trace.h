@@ -210,28 +210,34 @@ template <int K>
 struct LeafBuf {
     float d[K];
     int32_t leaf[K];  // leaf id = the leaf's rank in the static discovery order (inner_table)
+    int32_t n;        // entries held: slots [n, K) are empty (+inf, leaf 0)
 };
 
 template <int K>
 __device__ __forceinline__ void lb_clear(LeafBuf<K>& b) {
 #pragma unroll
     for (int j = 0; j < K; ++j) { b.d[j] = __builtin_inff(); b.leaf[j] = 0; }
+    b.n = 0;
 }
 
 // Insert a leaf discovered after every entry already held (larger discovery rank): it goes
-// behind every entry with distance <= dis, as the stable insertion sort does.
+// behind every entry with distance <= dis, as the stable insertion sort does. Only a full buffer
+// turns a leaf away (as the LDS buffer below): a leaf at distance +inf is not below an empty slot's
+// +inf, and the pass counts it whether it is held or not. It passes the empty slots by their index.
 template <int K>
 __device__ __forceinline__ void lb_insert(LeafBuf<K>& b, float dis, int32_t leaf) {
-    if (!(dis < b.d[K - 1])) return;
+    const int32_t held = b.n;
+    if (held == K && !(dis < b.d[K - 1])) return;
     b.d[K - 1] = dis;
     b.leaf[K - 1] = leaf;
 #pragma unroll
     for (int j = K - 1; j > 0; --j) {
-        if (b.d[j] < b.d[j - 1]) {
+        if (j > held || b.d[j] < b.d[j - 1]) {
             const float td = b.d[j]; b.d[j] = b.d[j - 1]; b.d[j - 1] = td;
             const int32_t tl = b.leaf[j]; b.leaf[j] = b.leaf[j - 1]; b.leaf[j - 1] = tl;
         }
     }
+    if (held < K) b.n = held + 1;
 }
 
 // Sorted-leaf scan with a rotating head: entry 0 is always the next leaf, the buffer shifts
@@ -241,6 +247,7 @@ __device__ __forceinline__ void lb_pop(LeafBuf<K>& b) {
 #pragma unroll
     for (int j = 0; j + 1 < K; ++j) { b.d[j] = b.d[j + 1]; b.leaf[j] = b.leaf[j + 1]; }
     b.d[K - 1] = __builtin_inff();
+    if (b.n > 0) --b.n;
 }
 
 // The same buffer held in LDS (lane-private column: entry j of lane ln at word 64 j + ln, no
@@ -289,7 +296,12 @@ __device__ __forceinline__ void lb_insert_lex(LdsLeafBuf<K>& b, float dis, int32
 
 template <int K>
 __device__ __forceinline__ void lb_insert(LdsLeafBuf<K>& b, float dis, int32_t leaf) {
-    if (!(dis < b.thr)) return;
+    // Only a full buffer turns a leaf away. A distance of +inf (a zero direction component on a box
+    // face: NaN and inf slabs) is not below the empty buffer's thr = +inf, and the pass counts the leaf
+    // whether it is held or not: a count above the entries held made the walk read the previous
+    // pass's entries behind them, the last of which is the bound this pass started from -- the
+    // re-walk then repeated itself for ever (tests/test_gpu_scale.py, the Monkey moved 2^17 out).
+    if (b.n == K && !(dis < b.thr)) return;
     int j = b.n < K ? b.n : K - 1;
     for (; j > 0; --j) {
         const float pd = b.d[64 * (j - 1)];

@@ -36,7 +36,13 @@ enum {
     ATR_OK = 0,
     ATR_E_INVALID = -1,     /* bad argument */
     ATR_E_IO = -2,          /* file could not be read */
-    ATR_E_NOMEM = -3,
+    ATR_E_NOMEM = -3,       /* memory could not be had, or a tree build passed its reference budget
+                               (atr_octree_build). No exception leaves an entry point that returns a
+                               status or a count: std::bad_alloc comes back as this, anything else as
+                               ATR_E_INVALID -- from the count-returning ones (atr_make_tiles,
+                               atr_make_shard_tiles, atr_balance_shard_tiles, atr_render_packed_size,
+                               atr_packed_pixel_map, atr_camera_pads_row), whose results are never
+                               negative, as that negative value */
     ATR_E_NOSCENE = -4,     /* render before atr_scene_upload */
     ATR_E_TREE_DEPTH = -5,  /* octree deeper than the traversal's mask stack (16 levels) */
     ATR_E_TREE_LAYOUT = -6, /* children boxes are not the parent's split-point octants
@@ -82,7 +88,17 @@ int atr_mesh_aabb(const atr_mesh* m, float aabb_out[6]);
 int atr_mesh_translate_to(atr_mesh* m, float aabb_inout[6], atr_vec3 new_center);
 
 /* build_KD_tree (kd_tree.cpp:20-64) -> build_oct_kd_tree (:67-288), SAH-named split, leaf
-   size max_faces (app.cpp:77 uses 300). Result is bit-identical to the reference's tree. */
+   size max_faces (app.cpp:77 uses 300). Result is bit-identical to the reference's tree.
+   The reference hands a triangle to every child box that holds one of its vertices (closed boxes), so
+   coincident triangles whose split point lies on a shared child-box face are copied into several
+   children at every level down to depth 64, and its build of such a mesh never ends (two equal
+   triangles in an axis-aligned plane at max_faces 1; a mesh moved 2^22 from the origin, whose vertices
+   collapse onto the float lattice). The build therefore bounds the tree's live primitive references
+   -- those of every node that is a leaf so far or still to be split -- by
+   min(2^31 - 1, 256 * nfaces + 2^20) and returns ATR_E_NOMEM, with *out untouched, as soon as they
+   pass it. A split never lowers that sum, so a mesh is refused whatever the order of the build; every
+   tree the reference does finish within the budget is unchanged (the largest ratio of references to
+   faces among the meshes the tests build is 3.0: DESIGN.md section 3, "Tree build"). */
 int atr_octree_build(const atr_mesh* m, uint32_t max_faces, atr_octree** out);
 /* A tree the caller already built (e.g. the reference's own KD_Tree walked into arrays):
    per node 6 floats (min, max) and children_start_position (0 = leaf); per leaf node its
@@ -92,8 +108,10 @@ int atr_octree_from_nodes(int32_t nnodes, const float* node_bounds, const int32_
                           const float* prim_vertices, const uint32_t* prim_face, atr_octree** out);
 /* f3: the same build on GPU `device` (atray_amd/csrc/build.hip): level-synchronous
    split sums and ordered vertex-in-box partitions as HIP kernels, nodes numbered in the
-   reference's LIFO order on the host. Result bit-identical to atr_octree_build. ms_out (may be
-   NULL): [0] wall time of the call incl. transfers, [1] device time of the build kernels. */
+   reference's LIFO order on the host. Result bit-identical to atr_octree_build, its reference budget
+   and ATR_E_NOMEM included: the budget is checked on the host from each level's counts before the next
+   level's primitive list is allocated or filled. ms_out (may be NULL): [0] wall time of the call incl.
+   transfers, [1] device time of the build kernels. */
 int atr_octree_build_device(const atr_mesh* m, uint32_t max_faces, int32_t device, atr_octree** out,
                             float ms_out[2]);
 void atr_octree_free(atr_octree* t);

@@ -66,6 +66,11 @@ def test_octree_bit_identical_to_oracle(asset):
     for k in ["nodes", "inner", "leaves", "empty_leaves", "leaf_prim_refs", "max_leaf"]:
         assert st[k] == os_[k], k
     assert st["depth"] < 16
+    same_tree(t, s)
+
+
+def same_tree(t, s):
+    """An engine tree's exported arrays against the oracle scene's tree_arrays(), bit for bit."""
     bounds, children, first, count, verts, face = t.export()
     nodes, otri, oface = s.tree_arrays()
     assert np.array_equal(bounds[:, :3].view(np.uint32), nodes["bmin"].view(np.uint32))

@@ -319,9 +319,15 @@ def test_row_obeys_the_bound(pair, name):
     it that the row did not treat as rejected: delta <= (sampled minimum of -(d . n)) - m, m = 32 eps P
     the documented margin (a delta of kTol is what the kernels assumed before and claims nothing). Every
     primitive treated as rejected has a sampled det below kTol everywhere."""
-    off, on = pair
     asset, leaf, cs, W, H, eye, facing = SCENES[name]
     upload(pair, asset, leaf, cs)
+    row_obeys_the_bound(pair, name, eye, must_fold=name != "cube")
+
+
+def row_obeys_the_bound(pair, name, eye, must_fold):
+    """The checks of test_row_obeys_the_bound on the scene both contexts hold, from `eye`; must_fold:
+    some cluster has to fold (the fold is engaged, not silently off)."""
+    off, on = pair
     row, boxes, edges = on.camera_pads_row(eye)
     n = len(row)
     assert n > 0
@@ -370,7 +376,7 @@ def test_row_obeys_the_bound(pair, name):
     assert np.allclose(gt, gl * (P * kt + ka) / (P * kl + ka), rtol=1e-5, atol=0.0)
     print(name, "clusters", n, "folded", int(folded.sum()), "at kTau", int((delta == K_TAU).sum()),
           "primitives rejected", int(rejected.sum()), "of", int(have.sum()))
-    if name != "cube":
+    if must_fold:
         assert folded.sum() > 0  # the fold is engaged
     # The other context's table is today's, built by today's kernel: its entries are, bit for bit, the
     # pair that cluster_grow returns in the folding kernel (boxes[:, 8], this context's tight growth)
