@@ -313,6 +313,15 @@ struct atr_ctx {
         hipStream_t stream = nullptr;
         bool used = false;
     } img_ws;
+    // Denoise workspace (atr_denoise, denoise.hip), grow-only and apart from all of the above: `color` =
+    // the two ping-pong images of 16-B colour records, `guides` = the 16-B normal and position records
+    // of the guides the call has; one per context, ordered between streams by `ev` as img_ws is.
+    struct DenoiseWS {
+        DevBuf color, guides;
+        hipEvent_t ev = nullptr;
+        hipStream_t stream = nullptr;
+        bool used = false;
+    } dn_ws;
 };
 
 namespace {
@@ -1403,6 +1412,9 @@ int atr_destroy(atr_ctx* c) try {
     for (DevBuf* d : {&c->tex_ws.mesh, &c->tex_ws.map, &c->tex_ws.aux, &c->img_ws.image, &c->img_ws.flags})
         if (d->p) (void)hipFree(d->p);
     if (c->img_ws.ev) (void)hipEventDestroy(c->img_ws.ev);
+    for (DevBuf* d : {&c->dn_ws.color, &c->dn_ws.guides})
+        if (d->p) (void)hipFree(d->p);
+    if (c->dn_ws.ev) (void)hipEventDestroy(c->dn_ws.ev);
     for (atr_ctx::PadSlot& q : c->pad_slot) {
         if (q.mem.p) (void)hipFree(q.mem.p);
         if (q.built) (void)hipEventDestroy(q.built);
@@ -2781,6 +2793,98 @@ int atr_texels_to_image(atr_ctx* c, const float* values, const int32_t* texel, i
         P.src_flag = flg[0];
         P.dst = image;
         HIPCHK(atr_launch_texel_fill(P, s));
+    }
+    HIPCHK(hipEventRecord(ws.ev, s));
+    HIPCHK(record_stop(c, s, nullptr));
+    HIPCHK(note_launch(c, s));
+    c->have_render = true;
+    c->last_stream = s;
+    c->last_ntiles = 0;
+    return ATR_OK;
+} ATR_ABI_CATCH
+
+void atr_default_denoise_params(atr_denoise_params* out) {
+    if (!out) return;
+    std::memset(out, 0, sizeof(*out));
+    out->passes = 5;
+    out->sigma_color = 0.01f;  // the scale of the renderer's noise at 1-4 spp, not of its signal
+    out->sigma_position = 0.0f;
+    out->normal_power_log2 = 5;
+}
+
+int atr_denoise(atr_ctx* c, const float* color, const atr_denoise_guides* guides, int32_t width, int32_t height,
+                const atr_denoise_params* params, float* out, uint32_t* framebuffer, void* stream) try {
+    if (!c || !params || !color || (!out && !framebuffer)) return ATR_E_INVALID;
+    if (width < 1 || width > kDenoiseMaxSide || height < 1 || height > kDenoiseMaxSide) return ATR_E_INVALID;
+    const atr_denoise_params& dp = *params;
+    if (dp.passes < 1 || dp.passes > kDenoiseMaxPasses || dp.normal_power_log2 < 0 ||
+        dp.normal_power_log2 > kDenoiseMaxNormalPower)
+        return ATR_E_INVALID;
+    if (!(dp.sigma_color >= 0.0f) || !std::isfinite(dp.sigma_color) || !(dp.sigma_position >= 0.0f) ||
+        !std::isfinite(dp.sigma_position))
+        return ATR_E_INVALID;
+    for (int32_t r : dp.reserved)
+        if (r) return ATR_E_INVALID;
+    const atr_denoise_guides none = {nullptr, nullptr, nullptr};
+    const atr_denoise_guides& g = guides ? *guides : none;
+    const bool colour_on = dp.sigma_color > 0.0f, position_on = g.position && dp.sigma_position > 0.0f;
+    // the per-pass constants, in f32 (atray.h); a term that is on needs every one of them finite and > 0
+    float kc[kDenoiseMaxPasses], kp[kDenoiseMaxPasses];
+    for (int p = 0; p < dp.passes; ++p) {
+        const float sf = float(1 << p);
+        const float sc = dp.sigma_color / sf, sp = dp.sigma_position * sf;
+        kc[p] = colour_on ? 1.0f / (sc * sc) : 0.0f;
+        kp[p] = position_on ? 1.0f / (sp * sp) : 0.0f;
+        if (colour_on && !(std::isfinite(kc[p]) && kc[p] > 0.0f)) return ATR_E_INVALID;
+        if (position_on && !(std::isfinite(kp[p]) && kp[p] > 0.0f)) return ATR_E_INVALID;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = the null stream (HIP convention)
+    atr_ctx::DenoiseWS& ws = c->dn_ws;
+    if (!ws.ev) HIPCHK(hipEventCreateWithFlags(&ws.ev, hipEventDisableTiming));
+    const size_t npix = size_t(width) * size_t(height), image = npix * sizeof(float4_t);
+    const size_t need_guides = image * ((g.normal ? 1 : 0) + (g.position ? 1 : 0));
+    if (!ws.color.p || ws.color.n < 2 * image || ws.guides.n < need_guides) {  // grow: after the last call that used it
+        if (ws.used) HIPCHK(hipEventSynchronize(ws.ev));
+        int rc;
+        if ((rc = ensure_buf(ws.color, 2 * image, false))) return rc;
+        if (need_guides && (rc = ensure_buf(ws.guides, need_guides, false))) return rc;
+    }
+    if (ws.used && ws.stream != s) HIPCHK(hipStreamWaitEvent(s, ws.ev, 0));
+    c->prog_active = false;
+    HIPCHK(hipEventRecord(c->ev_start, s));
+    ws.used = true;  // from here on kernels of this call may be in flight on s
+    ws.stream = s;
+    float4_t* img[2] = {static_cast<float4_t*>(ws.color.p), static_cast<float4_t*>(ws.color.p) + npix};
+    float4_t* rec = static_cast<float4_t*>(ws.guides.p);
+    DenoisePack K;
+    std::memset(&K, 0, sizeof(K));
+    K.color = color;
+    K.normal = g.normal;
+    K.position = g.position;
+    K.ident = g.ident;
+    K.npixels = int64_t(npix);
+    K.color4 = img[0];
+    K.normal4 = g.normal ? rec : nullptr;
+    K.position4 = g.position ? rec + (g.normal ? npix : 0) : nullptr;
+    HIPCHK(atr_launch_denoise_pack(K, s));
+    DenoisePass P;
+    std::memset(&P, 0, sizeof(P));
+    P.width = width;
+    P.height = height;
+    P.normal_power = dp.normal_power_log2;
+    P.normal4 = K.normal4;
+    P.position4 = K.position4;
+    for (int p = 0; p < dp.passes; ++p) {
+        const bool last = p == dp.passes - 1;
+        P.step = 1 << p;
+        P.kc = kc[p];
+        P.kp = kp[p];
+        P.src = img[p & 1];
+        P.dst = last ? nullptr : img[(p & 1) ^ 1];
+        P.out = last ? out : nullptr;
+        P.framebuffer = last ? framebuffer : nullptr;
+        HIPCHK(atr_launch_denoise_pass(P, g.normal != nullptr, position_on, colour_on, s));
     }
     HIPCHK(hipEventRecord(ws.ev, s));
     HIPCHK(record_stop(c, s, nullptr));

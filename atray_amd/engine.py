@@ -39,6 +39,7 @@ ATR_RAY_SKY, ATR_RAY_TRI, ATR_RAY_SPHERE, ATR_RAY_PLANE, ATR_RAY_INVALID = 0, 1,
 # atr_occluded_rays: the byte of a ray
 ATR_OCCL_VISIBLE, ATR_OCCL_OCCLUDED, ATR_OCCL_INVALID = 0, 1, 2
 ATR_TEXELS_FLIP = 1  # atr_mesh_texels: negate every normal
+ATR_DENOISE_EMPTY = 0xFFFFFFFF  # atr_denoise_guides.ident: an inert pixel (-1 in an int32 tensor)
 
 ERRORS = {-1: "ATR_E_INVALID", -2: "ATR_E_IO", -3: "ATR_E_NOMEM", -4: "ATR_E_NOSCENE",
           -5: "ATR_E_TREE_DEPTH", -6: "ATR_E_TREE_LAYOUT"}
@@ -123,6 +124,15 @@ class atr_texels_out(C.Structure):
                 ("point", C.c_void_p), ("normal", C.c_void_p)]
 
 
+class atr_denoise_params(C.Structure):
+    _fields_ = [("passes", C.c_int32), ("sigma_color", C.c_float), ("sigma_position", C.c_float),
+                ("normal_power_log2", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class atr_denoise_guides(C.Structure):
+    _fields_ = [("normal", C.c_void_p), ("position", C.c_void_p), ("ident", C.c_void_p)]
+
+
 class atr_tuning(C.Structure):
     _fields_ = [("xcd_chunk", C.c_int32), ("frame_rotate", C.c_int32), ("hybrid_a", C.c_int32),
                 ("hybrid_b", C.c_int32), ("path_batch_log2", C.c_int32), ("cluster_size", C.c_int32),
@@ -151,7 +161,7 @@ EXPORTS = [
     "atr_render_start_adaptive", "atr_render_adaptive_info", "atr_render_cull_counters",
     "atr_trace_rays", "atr_occluded_rays", "atr_gather_occlusion", "atr_gather_directions",
     "atr_radiance_rays", "atr_gather_radiance", "atr_mesh_texels", "atr_texels_to_image",
-    "atr_render_fold_counters", "atr_camera_pads_row",
+    "atr_render_fold_counters", "atr_camera_pads_row", "atr_default_denoise_params", "atr_denoise",
 ]
 # the diagnostic build's extra symbols (include/atray_diag.h; make -C atray_amd/csrc DIAG=1)
 DIAG_EXPORTS = ["atr_render_wave_trace", "atr_render_phase_clocks", "atr_render_path_counters",
@@ -216,6 +226,8 @@ def lib():
                                  vp], C.c_int),
         "atr_mesh_texels": ([vp, vp, i32, i32, i32, i64, P(atr_texels_out), P(i64), vp], C.c_int),
         "atr_texels_to_image": ([vp, vp, vp, i64, i32, i32, i32, C.c_float * 3, vp, vp], C.c_int),
+        "atr_default_denoise_params": ([P(atr_denoise_params)], None),
+        "atr_denoise": ([vp, vp, P(atr_denoise_guides), i32, i32, P(atr_denoise_params), vp, vp, vp], C.c_int),
         "atr_render_packed_size": ([vp, i32], i64),
         "atr_render_counters": ([vp, P(atr_camera), vp, i32, C.c_uint64, i32, i64 * 10], C.c_int),
         "atr_render_cull_counters": ([vp, P(atr_camera), vp, i32, C.c_uint64, i32, i64 * 5], C.c_int),
@@ -967,14 +979,77 @@ class Engine:
                                         C.c_void_p(stream) if stream else None), "texels to image")
         return image
 
-    def bake_lightmap(self, mesh, width, height, nsamples, bounces=None, t_max=None, seed=0, passes=2, flip=False):
+    def denoise(self, color, normal=None, position=None, ident=None, passes=5, sigma_color=0.01, sigma_position=0.0,
+                normal_power_log2=5, out=None, framebuffer=False, stream=None):
+        """atr_denoise: the edge-avoiding a-trous filter on an image (atray.h has the formulas). color: a
+        contiguous (H, W, 3) float32 tensor on the engine's device; the guides normal, position: the
+        same, or None; ident: a contiguous (H, W) int32 or uint32 tensor, or None (ATR_DENOISE_EMPTY, -1
+        as int32, marks a pixel that is left alone and never read). out: an (H, W, 3) float32 tensor to
+        write (it may be `color` itself), or None for a new one. Enqueued on `stream` (a raw HIP
+        stream), or torch's current one. Returns the image, or with framebuffer=True (the image, the
+        BGRX framebuffer as an (H, W) int32 tensor); valid once the stream has run, e.g. after wait()."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if (not isinstance(color, torch.Tensor) or color.dtype != torch.float32 or color.dim() != 3
+                or color.shape[2] != 3 or color.device != dev or not color.is_contiguous()):
+            raise ValueError(f"color: a contiguous (H, W, 3) float32 tensor on {dev} is required")
+        h, w = int(color.shape[0]), int(color.shape[1])
+        for name, a in (("normal", normal), ("position", position), ("out", out)):
+            if a is None:
+                continue
+            if (not isinstance(a, torch.Tensor) or a.dtype != torch.float32 or tuple(a.shape) != (h, w, 3)
+                    or a.device != dev or not a.is_contiguous()):
+                raise ValueError(f"{name}: a contiguous ({h}, {w}, 3) float32 tensor on {dev} is required")
+        if ident is not None:
+            kinds = (torch.int32,) + ((torch.uint32,) if hasattr(torch, "uint32") else ())
+            if (not isinstance(ident, torch.Tensor) or ident.dtype not in kinds or tuple(ident.shape) != (h, w)
+                    or ident.device != dev or not ident.is_contiguous()):
+                raise ValueError(f"ident: a contiguous ({h}, {w}) int32 or uint32 tensor on {dev} is required")
+        if out is None:
+            out = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
+        fb = torch.empty((h, w), dtype=torch.int32, device=dev) if framebuffer else None
+        ptr = lambda a: C.c_void_p(a.data_ptr()) if a is not None and a.numel() else None  # noqa: E731
+        guides = atr_denoise_guides(*[a.data_ptr() if a is not None and a.numel() else None
+                                      for a in (normal, position, ident)])
+        params = atr_denoise_params(int(passes), float(sigma_color), float(sigma_position), int(normal_power_log2))
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        check(lib().atr_denoise(self.h, ptr(color), C.byref(guides), w, h, C.byref(params), ptr(out), ptr(fb),
+                                C.c_void_p(stream) if stream else None), "denoise")
+        return (out, fb) if framebuffer else out
+
+    def render_guides(self, cam, stream=None):
+        """The denoiser's guides for a frame of `cam`: trace_rays on camera_rays(cam), then (normal,
+        position, ident) as (H, W, 3), (H, W, 3) float32 and (H, W) int32 tensors in the render's IMAGE
+        orientation. normal and position are surface_points' (the normal turned towards the eye);
+        ident is ATR_DENOISE_EMPTY (-1) where the ray met the sky or was invalid, else (kind << 28) |
+        (model + 1). Computed on torch's current stream, so pass that stream or None."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        h, w = int(cam.height), int(cam.width)
+        orig, dirs = (torch.from_numpy(a).to(dev) for a in camera_rays(cam))
+        hit, _ = self.trace_rays(orig, dirs, stream=stream, outputs=("t", "model", "kind", "normal"))
+        pos, nrm = surface_points(orig, dirs, hit["t"], hit["normal"])
+        kind, model = hit["kind"], hit["model"]
+        ident = torch.where((kind == ATR_RAY_SKY) | (kind == ATR_RAY_INVALID), torch.full_like(kind, -1),
+                            (kind << 28) | (model + 1))
+        return (nrm.reshape(h, w, 3).contiguous(), pos.reshape(h, w, 3).contiguous(),
+                ident.to(torch.int32).reshape(h, w).contiguous())
+
+    def bake_lightmap(self, mesh, width, height, nsamples, bounces=None, t_max=None, seed=0, passes=2, flip=False,
+                      denoise=None):
         """A lightmap of `mesh` in three device calls: mesh_texels, a hemisphere gather on the texels'
         points and normals, texels_to_image. bounces None: gather_occlusion (t_max: one bound for every
         texel, or None), the value visible / (visible + occluded) on all three channels and 0 where both
         are 0; an int: gather_radiance's rgb with that many bounces. `mesh` has to be the mesh of the
         uploaded scene, at the position it was uploaded with: the texels' points are taken from it, the
-        rays are traced in the uploaded scene. Returns (the image as a (height, width, 3) float32 tensor,
-        the texel dict of mesh_texels); on torch's current stream, complete on return."""
+        rays are traced in the uploaded scene. denoise: None, or a dict of denoise()'s keywords (passes,
+        sigma_color, sigma_position, normal_power_log2): the per-texel values, and the texels' normals
+        and points, are put into images with texels_to_image(passes=0), ident is 0 where slot >= 0 and
+        ATR_DENOISE_EMPTY elsewhere, the value image is denoised and read back at texel[], and those
+        values go into the dilation in place of the gathered ones. Returns (the image as a (height,
+        width, 3) float32 tensor, the texel dict of mesh_texels); on torch's current stream, complete on
+        return."""
         import torch
         dev = torch.device("cuda", self.device)
         tex = self.mesh_texels(mesh, width, height, flip=flip)
@@ -988,6 +1063,16 @@ class Engine:
         else:
             out, _ = self.gather_radiance(pts, nrm, nsamples, int(bounces), seed=seed, want=("rgb",))
             values = out["rgb"]
+        if denoise is not None:
+            bad = [k for k in denoise if k not in ("passes", "sigma_color", "sigma_position", "normal_power_log2")]
+            if bad:
+                raise ValueError(f"denoise: unknown entries {bad}")
+            col, nim, pim = (self.texels_to_image(v, tex["texel"], width, height, passes=0)
+                             for v in (values, nrm, pts))
+            h, w = int(col.shape[0]), int(col.shape[1])
+            ident = torch.where(tex["slot"] >= 0, 0, -1).to(torch.int32).reshape(h, w).contiguous()
+            den = self.denoise(col, normal=nim, position=pim, ident=ident, **denoise)
+            values = den.reshape(-1, 3)[tex["texel"].to(torch.int64)].contiguous()
         image = self.texels_to_image(values, tex["texel"], width, height, passes=passes)
         rc, _ = self.wait()
         check(rc, "bake lightmap")

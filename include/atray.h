@@ -29,7 +29,8 @@ extern "C" {
    or entry point changed. atr_occluded_rays likewise; atr_gather_occlusion, atr_gather_out and
    atr_gather_directions likewise; atr_radiance_rays and atr_radiance_out likewise;
    atr_gather_radiance and atr_gather_radiance_out likewise; atr_mesh_texels, atr_texels_out and
-   atr_texels_to_image likewise. */
+   atr_texels_to_image likewise; atr_denoise, atr_denoise_params, atr_denoise_guides and
+   atr_default_denoise_params likewise. */
 #define ATR_ABI_VERSION 2
 
 enum {
@@ -828,6 +829,69 @@ int atr_mesh_texels(atr_ctx* ctx, const atr_mesh* mesh, int32_t width, int32_t h
 int atr_texels_to_image(atr_ctx* ctx, const float* values, const int32_t* texel, int64_t ncovered,
                         int32_t width, int32_t height, int32_t passes, const float fill[3], float* image,
                         void* stream);
+
+/* Guided denoising of a frame or a lightmap: the edge-avoiding a-trous wavelet filter of Dammertz et al.
+   2010 (a 5x5 B3-spline tap pattern whose spacing doubles per pass; stopping weights from normal,
+   position, object id and colour), with rational weights 1 / (1 + x) where the paper has Gaussians, so
+   that no transcendental is involved: every f32 operation below is separately rounded
+   (tests/c/denoise_ref.c restates them in plain C), dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z and
+   len2(a) = dot(a, a).
+   Buffers. color and out: DEVICE, 3 f32 per pixel, IMAGE layout (pixel (x, y) at y*width + x); color is
+   required. guides == NULL means all three guide pointers are NULL. out == color (the same pointer) is
+   allowed: color and the guides are read in full before anything is written; any other overlap is the
+   caller's error and is not checked. framebuffer (optional): BGRX u32 per pixel, made from the result
+   by the renderer's own clamp and quantisation per channel, k = pl_max(0, pl_min(c, 1)) with pl_max(a,
+   b) = a > b ? a : b and pl_min(a, b) = a > b ? b : a, uint32_t(k * 255.0f) & 0xFF (0 for a NaN), then
+   b | g << 8 | r << 16; written for every pixel. At least one of out and framebuffer is non-NULL.
+   Inert pixels. Decided once, from the caller's inputs: a pixel is inert if ident is given and equals
+   ATR_DENOISE_EMPTY, or any of its three colour floats is not finite, or normal is given and any of its
+   three floats is not finite, or position is given and any of its three floats is not finite. An inert
+   pixel keeps its input colour bit for bit through every pass and is never used as a tap (sky pixels,
+   uncovered texels, NaNs from elsewhere).
+   Per-pass constants, computed on the host in f32: s = 1 << p; sc = sigma_color / float(s), kc = 1.0f /
+   (sc * sc) (the colour tolerance halves per pass, as in the paper); sp = sigma_position * float(s), kp
+   = 1.0f / (sp * sp). The colour term is on iff sigma_color > 0, the position term iff position is
+   given and sigma_position > 0.
+   Pass p (0 .. passes-1) for a pixel P at (x, y) that is not inert, c_* the colours at the start of the
+   pass: sum = 0,0,0, wsum = 0; for dy = -2..2 (outer), dx = -2..2 (inner): Q = (x + dx*s, y + dy*s);
+   skip Q if it lies outside the image, is inert, or (ident given) ident_Q != ident_P; else
+     w = h[dy+2] * h[dx+2], h = {1/16, 1/4, 3/8, 1/4, 1/16} (exact);
+     normal given: c = dot(n_P, n_Q); c = c > 0 ? c : 0 (a NaN gives 0); c = c*c, normal_power_log2
+       times; w = w * c;
+     position term on: dv = p_Q - p_P; with normal given e = dot(n_P, dv), e2 = e*e (the distance of Q
+       from P's tangent plane, so that a surface seen at a grazing angle is not cut apart), else e2 =
+       len2(dv); w = w * (1.0f / (1.0f + e2 * kp));
+     colour term on: d2 = len2(c_Q - c_P); w = w * (1.0f / (1.0f + d2 * kc));
+     skip Q unless w > 0 (drops zero, NaN and negative weights);
+     per channel sum = sum + c_Q * w; then wsum = wsum + w.
+   The pixel's new colour is sum / wsum (three divisions) if wsum > 0, else c_P. The centre tap is an
+   ordinary tap. Each pass reads only the state at its start; the last pass's state is `out`.
+   Asynchronous on `stream`; atr_render_wait covers it (tiles_done 0), atr_last_kernel_ms times it. No
+   scene is needed. The passes run in a grow-only denoise workspace of the context, apart from the
+   query, path, texel and image workspaces: two colour images of 16 B per pixel (r, g, b and the id),
+   and 16 B per pixel more for each of normal and position that is given (32 to 64 B per pixel); a call
+   on another stream than the last first waits for it on the GPU.
+   ATR_E_INVALID, with nothing enqueued or written: ctx, params or color NULL; out and framebuffer both
+   NULL; width or height outside 1..16,384; passes outside 1..8; normal_power_log2 outside 0..7; a sigma
+   that is negative, NaN or infinite; non-zero reserved; a term that is on whose kc or kp is, in any of
+   the `passes` passes, not finite and > 0. No struct and no ABI version change. */
+#define ATR_DENOISE_EMPTY 0xFFFFFFFFu
+typedef struct {
+    int32_t passes;            /* 1..8; pass p (from 0) has tap spacing s = 2^p */
+    float   sigma_color;       /* > 0: colour term on; 0: off */
+    float   sigma_position;    /* > 0: position term on; 0: off; ignored when position == NULL */
+    int32_t normal_power_log2; /* 0..7: the normal term is max(dot, 0)^(2^this); ignored when normal == NULL */
+    int32_t reserved[4];       /* must be 0 */
+} atr_denoise_params;
+typedef struct {               /* DEVICE pointers, IMAGE layout (pixel (x, y) at y*width + x); any may be NULL */
+    const float*    normal;    /* 3 per pixel; need not be unit */
+    const float*    position;  /* 3 per pixel */
+    const uint32_t* ident;     /* per pixel: taps with another id weigh 0; ATR_DENOISE_EMPTY = inert pixel */
+} atr_denoise_guides;
+void atr_default_denoise_params(atr_denoise_params* out);   /* 5, 0.01f, 0.0f, 5, zeros */
+int atr_denoise(atr_ctx* ctx, const float* color, const atr_denoise_guides* guides, int32_t width,
+                int32_t height, const atr_denoise_params* params, float* out, uint32_t* framebuffer,
+                void* stream);
 
 /* wait_for_render_from_camera_to_finish: 1 = still running after timeout_ms, 0 = done,
    <0 = error. tiles_done (optional) = tiles of the last render known complete (progress). */
