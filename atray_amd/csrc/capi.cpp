@@ -208,6 +208,10 @@ struct atr_ctx {
     float scene_box[6] = {0.f, 0.f, 0.f, 1.f, 1.f, 1.f};  // the models' vertex bounds (lo, hi): queue-sort cells
     atr_tuning tune = default_tuning();  // atr_set_tuning
     int64_t nclusters = 0;
+    // the tree models' leaves (discovery ranks) in model order, DModel::lf_base / lf_count, and per
+    // scene leaf its {first scene cluster, cluster count} (atr_camera_leaf_boxes_row)
+    int64_t nleaves = 0;
+    std::vector<uint32_t> leaf_clusters;
     // per-cell plan (atr_set_cell_plan) for images of cplan_w x cplan_h; cplan_gen invalidates
     // the block cache
     std::vector<uint8_t> cplan;
@@ -271,6 +275,10 @@ struct atr_ctx {
         uint64_t gen = 0;  // scene_gen of the table's scene; 0: empty
         int32_t rows = 0;
         bool wide = false;  // a COUNT launch's table: two pairs per cluster (cluster.h pads_entry)
+        // The rows' leaf boxes (RenderParams::lbox; cluster.h leaf_box_add) follow the pairs in the same
+        // buffer, built right after them on the same stream: one key, one build event, one set of
+        // readers, one cap. 0: the table has none (ATR_LEAF_BOX=0).
+        size_t lbox_off = 0;
         float eye[kMaxFrameCams][3];
         hipEvent_t built = nullptr;
         hipStream_t built_on = nullptr;
@@ -286,6 +294,8 @@ struct atr_ctx {
     bool facing_fold = true;
     // ATR_WAVE_CULL at atr_create (0 = the primary kernels test every cluster of a leaf per ray)
     bool wave_cull = true;
+    // ATR_LEAF_BOX at atr_create (0 = no table of leaf boxes: the primary passes insert every leaf)
+    bool leaf_box = true;
     // Ray queries' workspace (atr_trace_rays, query.hip), apart from the path workspaces and grow-only:
     // `rays` = {key, rank} and the key order for `cap` rays (12 B each; sorted batches only) and, in
     // its first 256 B, the head counter; `bins` = `nbins` arrival counters (zero between calls: the
@@ -952,6 +962,8 @@ hipError_t bind_pads(atr_ctx* c, RenderParams& P, int sched, hipStream_t s, atr_
     *used = nullptr;
     P.pads = nullptr;
     P.pads_stride = 0;
+    P.lbox = nullptr;
+    P.lbox_stride = 0;
     if (!c->camera_pads || c->nclusters <= 0 || c->nclusters > int64_t(1) << 30 || !atr_render_reads_pads(P, sched))
         return hipSuccess;
     const int32_t rows = P.nfcam > 0 ? P.nfcam : 1;
@@ -959,7 +971,11 @@ hipError_t bind_pads(atr_ctx* c, RenderParams& P, int sched, hipStream_t s, atr_
     const int32_t stride = int32_t(c->nclusters);
     // an instrumented launch reads the unfolded pair and the folded growth: a table of its own kind
     const bool wide = P.counters != nullptr;
-    const size_t bytes = size_t(rows) * size_t(stride) * sizeof(float2_t) * (wide ? 2 : 1);
+    const size_t pbytes = size_t(rows) * size_t(stride) * sizeof(float2_t) * (wide ? 2 : 1);
+    // the rows' leaf boxes behind the pairs (32-byte entries, 32-byte aligned), under the same cap
+    const bool boxes = c->leaf_box && c->nleaves > 0 && c->nleaves <= int64_t(1) << 30;
+    const size_t lbox_off = boxes ? (pbytes + 31) / 32 * 32 : 0;
+    const size_t bytes = boxes ? lbox_off + size_t(rows) * size_t(c->nleaves) * 2 * sizeof(float4_t) : pbytes;
     if (bytes > atr_ctx::kPadMaxBytes) return hipSuccess;
     PadEyes eyes;
     std::memset(&eyes, 0, sizeof(eyes));
@@ -1005,16 +1021,26 @@ hipError_t bind_pads(atr_ctx* c, RenderParams& P, int sched, hipStream_t s, atr_
         if ((e = atr_launch_camera_pads(c->d_scene, eyes, rows, stride, c->facing_fold, wide, static_cast<float2_t*>(sl->mem.p),
                                         nullptr, nullptr, nullptr, s)) != hipSuccess)
             return e;
+        if (boxes && (e = atr_launch_camera_leaf_boxes(c->d_scene, eyes, rows, stride, wide, static_cast<const float2_t*>(sl->mem.p),
+                                                       int32_t(c->nleaves),
+                                                       reinterpret_cast<float4_t*>(static_cast<char*>(sl->mem.p) + lbox_off),
+                                                       s)) != hipSuccess)
+            return e;
         if ((e = hipEventRecord(sl->built, s)) != hipSuccess) return e;
         sl->built_on = s;
         sl->gen = c->scene_gen;
         sl->rows = rows;
         sl->wide = wide;
+        sl->lbox_off = lbox_off;
         std::memcpy(sl->eye, eyes.e, sizeof(eyes.e));
     }
     sl->last_use = ++c->pad_clock;
     P.pads = static_cast<const float2_t*>(sl->mem.p);
     P.pads_stride = stride;
+    if (sl->lbox_off) {
+        P.lbox = reinterpret_cast<const float4_t*>(static_cast<const char*>(sl->mem.p) + sl->lbox_off);
+        P.lbox_stride = int32_t(c->nleaves);
+    }
     *used = sl;
     return hipSuccess;
 }
@@ -1333,6 +1359,9 @@ int atr_create(int device, atr_ctx** out) try {
     // ATR_FACING_FOLD=0: this context's table holds the unfolded loose growths (A/B runs and tests; same
     // output bits either way)
     if (const char* v = std::getenv("ATR_FACING_FOLD")) c->facing_fold = !(v[0] == '0' && v[1] == '\0');
+    // ATR_LEAF_BOX=0: this context builds no table of leaf boxes and its primary passes insert every
+    // leaf (A/B runs and tests; same output bits either way)
+    if (const char* v = std::getenv("ATR_LEAF_BOX")) c->leaf_box = !(v[0] == '0' && v[1] == '\0');
     const int rc = [&]() -> int {  // any failure below releases what was created (atr_destroy)
         HIPCHK(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
         HIPCHK(hipEventCreate(&c->ev_start));
@@ -1485,6 +1514,8 @@ int atr_scene_upload(atr_ctx* c, const atr_material* mats, int32_t nmats, const 
     c->max_depth = 0;
     c->max_inner = 0;
     c->nclusters = 0;
+    c->nleaves = 0;
+    c->leaf_clusters.clear();
     float box[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
     for (int32_t i = 0; i < nmodels; ++i)
         for (const V3& v : models[i].mesh->m.vertices) {
@@ -1544,6 +1575,14 @@ int atr_scene_upload(atr_ctx* c, const atr_material* mats, int32_t nmats, const 
             if (c->nclusters + int64_t(PT.nclusters) > int64_t(UINT32_MAX)) return ATR_E_INVALID;
             dm.cl_base = uint32_t(c->nclusters);  // the model's place in the scene-wide cluster numbering
             dm.cl_count = uint32_t(PT.nclusters);
+            if (c->nleaves + int64_t(PT.nleaves) > int64_t(UINT32_MAX)) return ATR_E_INVALID;
+            dm.lf_base = uint32_t(c->nleaves);  // and in the scene-wide leaf numbering
+            dm.lf_count = uint32_t(PT.nleaves);
+            for (size_t k = 0; k < PT.nleaves; ++k) {
+                c->leaf_clusters.push_back(dm.cl_base + PT.cl_range[2 * k]);
+                c->leaf_clusters.push_back(PT.cl_range[2 * k + 1]);
+            }
+            c->nleaves += int64_t(PT.nleaves);
             c->nclusters += int64_t(PT.nclusters);
             if ((rc = up(PT.nodes, dm.nodes)) || (rc = up(PT.leaf_range, dm.leaf_range))) return rc;
             if (PT.tris.empty()) PT.tris.resize(1);
@@ -2345,7 +2384,7 @@ int atr_render_wave_trace(atr_ctx* c, const atr_camera* cam, const atr_tile* til
 
 // One instrumented (COUNT) render; h = the 16 device counters (render.hip: [0..9] work counters,
 // [10..15] phase clocks, zero unless built with -DATR_PHASE_CLOCKS).
-constexpr int kCounterSlots = 32;
+constexpr int kCounterSlots = 34;
 static int count_launch(atr_ctx* c, const atr_camera* cam, const atr_tile* tiles, int32_t ntiles, uint64_t seed,
                         int32_t variant, unsigned long long h[kCounterSlots]) {
     if (!c || !cam || ntiles < 0 || (ntiles && !tiles)) return ATR_E_INVALID;
@@ -2412,6 +2451,44 @@ int atr_render_fold_counters(atr_ctx* c, const atr_camera* cam, const atr_tile* 
     out[0] = int64_t(h[30]);  // (ray, cluster) pairs past the unfolded loose box that fail the folded one
     out[1] = int64_t(h[31]);  // the primitives screened for them
     return ATR_OK;
+} ATR_ABI_CATCH
+
+int atr_render_leaf_box_counters(atr_ctx* c, const atr_camera* cam, const atr_tile* tiles, int32_t ntiles,
+                                 uint64_t seed, int32_t variant, int64_t out[2]) try {
+    if (!out) return ATR_E_INVALID;
+    unsigned long long h[kCounterSlots];
+    const int rc = count_launch(c, cam, tiles, ntiles, seed, variant, h);
+    if (rc != ATR_OK) return rc;
+    out[0] = int64_t(h[32]);  // (lane, leaf) visits whose leaf the product passes leave out
+    out[1] = int64_t(h[33]);  // those of them in which a cluster passed the table's loose box
+    return ATR_OK;
+} ATR_ABI_CATCH
+
+int64_t atr_camera_leaf_boxes_row(atr_ctx* c, const float eye[3], float* row, int32_t* ranges, int64_t cap) try {
+    if (!c || !eye || cap < 0) return ATR_E_INVALID;
+    if (!c->d_scene) return ATR_E_NOSCENE;
+    const int64_t n = c->nleaves, ncl = c->nclusters;
+    if (n <= 0 || ncl <= 0) return 0;
+    if (n > int64_t(1) << 30 || ncl > int64_t(1) << 30) return ATR_E_INVALID;
+    if (!row || cap < n) return n;  // the count alone
+    HIPCHK(hipSetDevice(c->device));
+    PadEyes eyes;
+    std::memset(&eyes, 0, sizeof(eyes));
+    eyes.e[0][0] = eye[0], eyes.e[0][1] = eye[1], eyes.e[0][2] = eye[2];
+    // as bind_pads builds a one-camera launch's table: the row of growths, then the boxes from it
+    DevTmp d_tab, d_box;
+    HIPCHK(hipMalloc(&d_tab.p, size_t(ncl) * sizeof(float2_t)));
+    HIPCHK(hipMalloc(&d_box.p, size_t(n) * 2 * sizeof(float4_t)));
+    HIPCHK(hipMemset(d_tab.p, 0, size_t(ncl) * sizeof(float2_t)));
+    HIPCHK(hipMemset(d_box.p, 0, size_t(n) * 2 * sizeof(float4_t)));
+    HIPCHK(atr_launch_camera_pads(c->d_scene, eyes, 1, int32_t(ncl), c->facing_fold, 0, static_cast<float2_t*>(d_tab.p),
+                                  nullptr, nullptr, nullptr, nullptr));
+    HIPCHK(atr_launch_camera_leaf_boxes(c->d_scene, eyes, 1, int32_t(ncl), 0, static_cast<const float2_t*>(d_tab.p),
+                                        int32_t(n), static_cast<float4_t*>(d_box.p), nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(row, d_box.p, size_t(n) * 2 * sizeof(float4_t), hipMemcpyDeviceToHost));
+    if (ranges) std::memcpy(ranges, c->leaf_clusters.data(), size_t(n) * 2 * sizeof(uint32_t));
+    return n;
 } ATR_ABI_CATCH
 
 int64_t atr_camera_pads_row(atr_ctx* c, const float eye[3], float* row, float* boxes, float* edges, int64_t cap) try {

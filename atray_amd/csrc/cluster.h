@@ -17,6 +17,9 @@
 //     cluster as f16 integer multiples of one step) is within a bounded margin of the computed det
 //     (cluster_step), which widens the screen's band.
 //     Back-facing primitives (det < kTol) are screened out the same way in both cases.
+//   * one level up, per (camera, leaf): the primary table kernels' passes leave out a leaf whose box
+//     -- the bounds of its clusters' loose boxes for that camera -- the ray misses (leaf_box_add below;
+//     trace.h leaf_box_miss).
 //   * inside the leaf the reference keeps the FIRST primitive (leaf order) with the smallest t
 //     below the incoming best (strict <, kd_tree.cpp:440-456); clusters change the visiting
 //     order, so equal t is resolved by the leaf rank, and a best carried in from an earlier
@@ -249,6 +252,66 @@ __device__ __forceinline__ bool cluster_hull_keep(V3 o, const WaveHull& hl, floa
     return !cull || !(fmaxf(fmaxf(gx, gy), gz) < __builtin_inff());
 }
 
+// The leaf box of a (camera, leaf) pair: per axis, bounds of every cluster box of the
+// leaf grown by the row's own loose growth of that cluster -- the folded g.x the product kernels read
+// -- and by a slack for the slab arithmetic, in fold_box's form: g (1 + 2^-10) + 2^-20 F_axis, F the
+// far face's distance from the eye. A ray from the eye whose plain slab test misses [LO, HI]
+// (trace.h leaf_box_miss) fails cluster_pads' loose test on every cluster of the leaf. All in f32, one
+// operation at a time (-ffp-contract=off), so that a test can restate it; every bound is moved one
+// float outward after its last rounding, so the rounding of the construction itself only widens it.
+// An entry is {LO.xyz, bits(flag)}{HI.xyz, 0}: kLeafBoxTest (0) the slab test decides, kLeafBoxEmpty
+// a leaf without clusters (always left out: LO = +inf, HI = -inf would not fail a slab test),
+// kLeafBoxKeep a leaf that is never left out -- a NaN, an infinite operand or growth, or a bound
+// whose difference from the eye overflows, so that the test's own operands are always finite.
+
+// The float below / above x (finite x; a zero steps to the smallest subnormal of that sign).
+__device__ __forceinline__ float f32_below(float x) {
+    const uint32_t u = __float_as_uint(x);
+    if (x > 0.f) return __uint_as_float(u - 1u);
+    if (x < 0.f) return __uint_as_float(u + 1u);
+    return x == 0.f ? __uint_as_float(0x80000001u) : x;
+}
+__device__ __forceinline__ float f32_above(float x) { return -f32_below(-x); }
+
+struct LeafBox {
+    float lo[3], hi[3];
+    bool bad;
+};
+__device__ __forceinline__ void leaf_box_init(LeafBox& b) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) { b.lo[a] = __builtin_inff(); b.hi[a] = -__builtin_inff(); }
+    b.bad = false;
+}
+// One cluster's part: record words lo, hi and the row's loose growth gl of that cluster.
+__device__ __forceinline__ void leaf_box_add(LeafBox& b, V3 eye, float4_t lo, float4_t hi, float gl) {
+    constexpr float inf = __builtin_inff();
+    const float l[3] = {lo.x, lo.y, lo.z}, h[3] = {hi.x, hi.y, hi.z}, e[3] = {eye.x, eye.y, eye.z};
+    const float g = gl * 1.0009765625f;  // 1 + 2^-10
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float F = fmaxf(fabsf(l[a] - e[a]), fabsf(h[a] - e[a]));
+        const float slack = g + 9.5367432e-7f * F;  // 2^-20 F
+        const float x0 = f32_below(l[a] - slack), x1 = f32_above(h[a] + slack);
+        // (the comparisons are false for a NaN, which fminf and fmaxf would drop)
+        if (!(slack < inf) || !(fabsf(x0) < inf) || !(fabsf(x1) < inf)) b.bad = true;
+        b.lo[a] = fminf(b.lo[a], x0);
+        b.hi[a] = fmaxf(b.hi[a], x1);
+    }
+}
+// The entry of a leaf of n clusters, all added.
+__device__ __forceinline__ void leaf_box_entry(const LeafBox& b, uint32_t n, V3 eye, float4_t& e0, float4_t& e1) {
+    constexpr float inf = __builtin_inff();
+    const float e[3] = {eye.x, eye.y, eye.z};
+    bool bad = b.bad;
+#pragma unroll
+    for (int a = 0; a < 3; ++a)  // the slab test's first operation, on its own operands
+        if (!(fabsf(b.lo[a] - e[a]) < inf) || !(fabsf(b.hi[a] - e[a]) < inf)) bad = true;
+    const uint32_t flag = n == 0 ? kLeafBoxEmpty : bad ? kLeafBoxKeep : kLeafBoxTest;
+    const bool box = flag == kLeafBoxTest;
+    e0 = float4_t{box ? b.lo[0] : 0.f, box ? b.lo[1] : 0.f, box ? b.lo[2] : 0.f, __uint_as_float(flag)};
+    e1 = float4_t{box ? b.hi[0] : 0.f, box ? b.hi[1] : 0.f, box ? b.hi[2] : 0.f, 0.f};
+}
+
 // Screen of 8 primitives g .. g + 7 of n: words a0, a1 hold (nx, ny) of slots g .. g + 7 as f16,
 // z the nz of slots g .. g + 7 (two per word). Bit j: slot g + j needs the full test.
 // Bit j set iff the f16 dot D_j of slot g + j lies in (blo, ahi]: the det band mapped back through
@@ -312,9 +375,11 @@ __device__ __forceinline__ size_t pads_entry(size_t c) { return COUNT ? 2 * c : 
 // mask of the primitives (slot 16 c + bit) that still need the full test.
 // PADS: the growths of the box come from the camera's table row `pads` (indexed by the model's
 // cluster), loaded with the cluster record, instead of being computed from the origin.
+// wskip (COUNT with PADS): the leaf box says the ray misses this leaf; counted if the cluster passes.
 template <bool COUNT, bool EARLY = true, bool PADS = false>
 __device__ __forceinline__ uint32_t cluster_cands(const Ray& r, const DModel& m, uint32_t c, float4_t lo, float4_t hi,
-                                                  float best, Ctr& ct, const float2_t* pads = nullptr) {
+                                                  float best, Ctr& ct, const float2_t* pads = nullptr,
+                                                  [[maybe_unused]] bool wskip = false) {
     // (the COUNT build's table is wide, pads_entry below: the unfolded pair, then the folded growth)
     float2_t g;
     if constexpr (PADS) g = pads[pads_entry<COUNT>(c)];
@@ -345,6 +410,7 @@ __device__ __forceinline__ uint32_t cluster_cands(const Ray& r, const DModel& m,
     if constexpr (PADS && COUNT) {
         float fl, fh;
         if (!cluster_pads(r, sr, lo, hi, gfold, best, fl, fh)) { ct.fold_box += 1; ct.fold_screen += n; }
+        else if (wskip) ct.lb_unsound += 1;  // wskip: the product pass leaves this visit's leaf out
     }
     const uint32_t slots = (2u << (n - 1)) - 1u;  // [0, n), 1 <= n <= 16
     const float q = hi.w;

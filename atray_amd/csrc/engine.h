@@ -141,6 +141,9 @@ struct DModel {
     // the model's clusters in the scene-wide cluster numbering (the tree models' clusters in model
     // order): the index of the per-camera table of box growths (RenderParams::pads)
     uint32_t cl_base, cl_count;
+    // and its leaves (discovery ranks, what cl_range is indexed by) in the scene-wide leaf numbering:
+    // the index of the per-camera table of leaf boxes (RenderParams::lbox)
+    uint32_t lf_base, lf_count;
 };
 
 struct DMaterial { float ex, ey, ez, rx, ry, rz, scatter, pad; };
@@ -218,6 +221,13 @@ struct RenderParams {
     // clusters are tested against the wave's direction hull before the per-ray tests. Read by
     // HYBRID's primary kernels only; same output bits either way.
     int32_t wave_cull;
+    // The primary table kernels' leaf boxes (cluster.h leaf_box): row f holds one
+    // 32-byte entry {LO.xyz, bits(flag)}{HI.xyz, 0} per leaf of the scene (lbox_stride entries per
+    // row), the bounds of the leaf's clusters grown by the row's own loose growths. Non-null (only
+    // with pads), a lane's pass leaves out the leaves whose box its ray misses. Last in the struct and
+    // read by the kernels that read pads only; same output bits either way.
+    const float4_t* lbox;
+    int32_t lbox_stride;
 };
 
 // The eyes of a launch's cameras, by value, for the kernel that fills the table.

@@ -519,6 +519,7 @@ int atr::pack_tree(const HostTree& T, int cluster_size, PackedTree& P) {
         return out;
     };
     P.leaf_range = by_rank(range);
+    for (int32_t n = 0; n < T.nnodes; ++n) P.nleaves = std::max(P.nleaves, size_t(leaf_rank[size_t(n)] + 1));
     P.tris.resize(nprims);
     for (size_t k = 0; k < nprims; ++k) P.tris[k] = make_tri(&T.prim_vertices[9 * k], T.prim_face[k]);
     const size_t np = nprims ? nprims : 1;

@@ -62,6 +62,7 @@ struct PackedTree {
     size_t nclusters = 0;
     std::vector<uint32_t> clus;        // 4 x kClusterBlock u32 per cluster: {lo, P}{hi, q}, normal words
     std::vector<uint32_t> cl_range;    // 2 per leaf rank: first cluster, cluster count
+    size_t nleaves = 0;                // leaf ranks in use (a root that never split: 1)
     std::vector<float4_t> prim;        // 3 per slot (kMaxClusterSize slots per cluster): 48-B records
     int32_t max_depth = 0;
     bool near_ok = false;              // traverse_pass_near's register stack fits the tree

@@ -14,6 +14,9 @@ int atr_render_reads_pads(const atr::RenderParams& P, int sched);
 hipError_t atr_launch_camera_pads(const atr::DScene* scene, const atr::PadEyes& eyes, int32_t nrows, int32_t stride,
                                   int fold, int wide, atr::float2_t* table, atr::float2_t* info, atr::float4_t* boxes,
                                   float* edges, hipStream_t s);
+hipError_t atr_launch_camera_leaf_boxes(const atr::DScene* scene, const atr::PadEyes& eyes, int32_t nrows, int32_t stride,
+                                        int wide, const atr::float2_t* pads, int32_t lstride, atr::float4_t* lbox,
+                                        hipStream_t s);
 hipError_t atr_launch_traced_finish(unsigned long long* slots, unsigned long long* out, hipStream_t s);
 hipError_t atr_launch_unpack(const atr::DBlock* blocks, int32_t nblocks, int32_t width, const uint32_t* packed,
                              uint32_t* image, hipStream_t s);

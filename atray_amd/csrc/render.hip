@@ -175,8 +175,11 @@ __global__ __launch_bounds__(256, OCC) void render_kernel(RenderParams P) {
             // the camera's row: the frame index and the stride are wave-uniform, the base stays in SGPRs
             const int32_t row = P.nfcam > 0 ? __builtin_amdgcn_readfirstlane(fidx) : 0;
             const float2_t* pads = uniform_global(P.pads) + pads_entry<COUNT>(size_t(int64_t(row) * P.pads_stride));
+            // and its row of leaf boxes (null: switched off, or no table)
+            const float4_t* lbox = uniform_global(P.lbox);
+            if (lbox) lbox += 2 * size_t(int64_t(row) * P.lbox_stride);
             intersect_scene<SCHED, FlavPrimaryPads, COUNT>(S, eye, dir, active, id, err, ct, P.hyb_a, P.hyb_b, pads,
-                                                           P.wave_cull);
+                                                           P.wave_cull, lbox);
         } else {
             intersect_scene<SCHED, FlavPrimary, COUNT>(S, eye, dir, active, id, err, ct, P.hyb_a, P.hyb_b, nullptr,
                                                        P.wave_cull);
@@ -316,6 +319,18 @@ __global__ __launch_bounds__(256, OCC) void render_kernel(RenderParams P) {
                 if (lane == 0 && x2) atomicAdd(C + 30 + k, (unsigned long long)x2);
             }
         }
+        // counters[32..33] (the table build): the leaf boxes' (lane, leaf) visits left out by the
+        // product kernels, and the unsound ones among them
+        if constexpr (PADS) {
+            uint32_t f[2] = {ct.lb_skip, ct.lb_unsound};
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                uint32_t x2 = f[k];
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) x2 += __shfl_xor(x2, off);
+                if (lane == 0 && x2) atomicAdd(C + 32 + k, (unsigned long long)x2);
+            }
+        }
         // counters[10..15]: wave clocks in DFS passes, lane-private scans, dealt rounds, whole
         // wave, per-step preparation, whole FLAT/HYBRID scan (phases: diagnostic build only)
         if (lane == 0) {
@@ -451,6 +466,42 @@ __global__ __launch_bounds__(256) void camera_fold_kernel(const DScene* __restri
     }
 }
 
+// The table of leaf boxes (RenderParams::lbox; cluster.h leaf_box_add): thread (x, y) builds the entry
+// of scene leaf x for camera y from the leaf's cluster records and the loose growths that row y of the
+// table of box growths holds for them -- what the primary kernels read: the folded growth, or the
+// unfolded one in a context without the fold (WIDE: a COUNT launch's table, the second pair's).
+// Runs after the kernel that writes `pads`, on its stream. lstride = the scene's leaf count.
+template <bool WIDE>
+__global__ __launch_bounds__(256) void camera_leaf_box_kernel(const DScene* __restrict__ S, PadEyes eyes,
+                                                              int32_t stride, const float2_t* __restrict__ pads,
+                                                              int32_t lstride, float4_t* __restrict__ lbox) {
+    const uint32_t x = blockIdx.x * 256u + threadIdx.x;
+    if (x >= uint32_t(lstride)) return;
+    const int32_t f = __builtin_amdgcn_readfirstlane(int32_t(blockIdx.y));
+    const V3 eye = mk(eyes.e[f][0], eyes.e[f][1], eyes.e[f][2]);
+    const int32_t nmodels = S->nmodels;
+    for (int32_t i = 0; i < nmodels; ++i) {
+        const DModel& m = S->models[i];
+        const uint32_t lf = x - m.lf_base;  // wraps below the model's first leaf
+        if (!m.has_tree || lf >= m.lf_count) continue;
+        const uint2_t cr = load_range(m.cl_range, int32_t(lf));
+        LeafBox b;
+        leaf_box_init(b);
+        for (uint32_t k = 0; k < cr.y; ++k) {
+            const uint32_t c = cr.x + k;
+            const size_t e = size_t(f) * size_t(stride) + m.cl_base + c;
+            const float gl = WIDE ? pads[2 * e + 1].x : pads[e].x;
+            leaf_box_add(b, eye, m.clus[kClusterBlock * size_t(c)], m.clus[kClusterBlock * size_t(c) + 1], gl);
+        }
+        float4_t e0, e1;
+        leaf_box_entry(b, cr.y, eye, e0, e1);
+        const size_t o = 2 * (size_t(f) * size_t(lstride) + x);
+        lbox[o] = e0;
+        lbox[o + 1] = e1;
+        return;
+    }
+}
+
 // Sum the 64 traced-ray counters of a launch into the caller's accumulator and clear them.
 __global__ __launch_bounds__(64) void traced_finish_kernel(unsigned long long* __restrict__ slots,
                                                           unsigned long long* __restrict__ out) {
@@ -574,6 +625,20 @@ extern "C" hipError_t atr_launch_camera_pads(const atr::DScene* scene, const atr
         if (wide) hipLaunchKernelGGL(camera_pads_kernel<true>, gp, dim3(256), 0, s, scene, eyes, stride, table);
         else hipLaunchKernelGGL(camera_pads_kernel<false>, gp, dim3(256), 0, s, scene, eyes, stride, table);
     }
+    return hipGetLastError();
+}
+
+// Fill rows [0, nrows) of a table of leaf boxes for the scene's `lstride` leaves from the rows of the
+// table of box growths `pads` (stride pairs per row; wide as above), after its build on s.
+extern "C" hipError_t atr_launch_camera_leaf_boxes(const atr::DScene* scene, const atr::PadEyes& eyes, int32_t nrows,
+                                                   int32_t stride, int wide, const atr::float2_t* pads, int32_t lstride,
+                                                   atr::float4_t* lbox, hipStream_t s) {
+    using namespace atr;
+    if (nrows <= 0 || lstride <= 0) return hipSuccess;
+    if (nrows > kMaxFrameCams || stride <= 0 || !pads || !lbox) return hipErrorInvalidValue;
+    const dim3 g(unsigned((lstride + 255) / 256), unsigned(nrows));
+    if (wide) hipLaunchKernelGGL(camera_leaf_box_kernel<true>, g, dim3(256), 0, s, scene, eyes, stride, pads, lstride, lbox);
+    else hipLaunchKernelGGL(camera_leaf_box_kernel<false>, g, dim3(256), 0, s, scene, eyes, stride, pads, lstride, lbox);
     return hipGetLastError();
 }
 

@@ -242,7 +242,7 @@ constexpr unsigned long long kKeyInit = (static_cast<unsigned long long>(0x7F7FF
 #endif
 
 // Flavours of the clustered scan: the one template argument F of every piece below. The pieces
-// explain the members they read: SEED flat_begin; UT, LDSB, NEAR flat_pass; HYB, PADS, WCULL
+// explain the members they read: SEED flat_begin; UT, LDSB, NEAR, LBOX flat_pass; HYB, PADS, WCULL
 // flat_leaf_step. UO: every ray of the wave has the same origin. UV: the hit's barycentrics feed an
 // output (else FlatLds has no u/v rows). EARLY: the flavour's bit of ATR_EARLY_NRM (cluster.h).
 // CAMERA rays (one origin, coherent: HYBRID's wave-walked passes, LDS leaf buffer); PRIMARY-only
@@ -251,18 +251,18 @@ constexpr unsigned long long kKeyInit = (static_cast<unsigned long long>(0x7F7FF
 // leaf buffer, HYBRID's choice per step); OCCLUSION queries (BOUNCE without u and v, seeded key).
 // clang-format off
 struct FlavCamera      { static constexpr bool HYB = true,  LDSB = true,  UO = true,  UT = true,  UV = true,
-                         NEAR = false, PADS = false, WCULL = false, SEED = false; static constexpr int EARLY = 2; };
+                         NEAR = false, PADS = false, WCULL = false, SEED = false, LBOX = false; static constexpr int EARLY = 2; };
 struct FlavPrimary     { static constexpr bool HYB = true,  LDSB = true,  UO = true,  UT = true,  UV = false,
-                         NEAR = false, PADS = false, WCULL = true,  SEED = false; static constexpr int EARLY = 1; };
+                         NEAR = false, PADS = false, WCULL = true,  SEED = false, LBOX = false; static constexpr int EARLY = 1; };
 struct FlavPrimaryPads { static constexpr bool HYB = true,  LDSB = true,  UO = true,  UT = true,  UV = false,
-                         NEAR = false, PADS = true,  WCULL = true,  SEED = false; static constexpr int EARLY = 8; };
+                         NEAR = false, PADS = true,  WCULL = true,  SEED = false, LBOX = true;  static constexpr int EARLY = 8; };
 struct FlavHybBounce   { static constexpr bool HYB = true,  LDSB = false, UO = false, UT = false, UV = true,
-                         NEAR = false, PADS = false, WCULL = false, SEED = false; static constexpr int EARLY = 4; };
+                         NEAR = false, PADS = false, WCULL = false, SEED = false, LBOX = false; static constexpr int EARLY = 4; };
 struct FlavBounce      { static constexpr bool HYB = ATR_BOUNCE_HYB != 0, LDSB = true, UO = false, UT = false,
-                         UV = true, NEAR = true, PADS = false, WCULL = false, SEED = false;
+                         UV = true, NEAR = true, PADS = false, WCULL = false, SEED = false, LBOX = false;
                          static constexpr int EARLY = 4; };
 struct FlavOcclusion   { static constexpr bool HYB = false, LDSB = true,  UO = false, UT = false, UV = false,
-                         NEAR = true,  PADS = false, WCULL = false, SEED = true;  static constexpr int EARLY = 1; };
+                         NEAR = true,  PADS = false, WCULL = false, SEED = true,  LBOX = false; static constexpr int EARLY = 1; };
 // clang-format on
 
 // One full test of candidate `slot` for the ray q of owner lane `ow`: lowers the owner's (t bits,
@@ -446,8 +446,13 @@ __device__ __forceinline__ FlatQ flat_begin(const Ray& r, const DModel& m, bool 
 // One DFS pass (kd_tree.cpp:363-435) for every lane with `need`; its sorted leaves wait in LDS.
 // F::UT: the wave walks its passes together (traverse_pass_wave: coherent rays). F::LDSB: the pass
 // inserts straight into the LDS columns. F::NEAR (with LDSB): near-first passes (traverse_pass_near).
+// F::LBOX (with UT; the primary table flavour): the pass leaves out the leaves whose box in `lbox` --
+// the camera's row of the per-camera table of leaf boxes at this model's first leaf, wave-uniform,
+// null when switched off -- the lane's ray misses (trace.h examine_inner).
 template <class F, bool COUNT, int K = kLeafBuf>
-__device__ __forceinline__ void flat_pass(const Ray& r, const DModel& m, int w, int ln, FlatQ& q, int& err, Ctr& ct) {
+__device__ __forceinline__ void flat_pass(const Ray& r, const DModel& m, int w, int ln, FlatQ& q, int& err, Ctr& ct,
+                                          const float4_t* lbox = nullptr) {
+    static_assert(!F::LBOX || (F::UT && F::PADS), "the boxes are sized by the table's growths; uniform leaf ranks");
     FlatLds<K, F::UV>& L = flat_lds<K, F::UV>();
     // the re-walk bound: the last leaf of the previous pass's full buffer (entry K - 1 of the column)
     const float bd = q.rewalk ? L.lbd[w][K - 1][ln] : -__builtin_inff();
@@ -463,7 +468,7 @@ __device__ __forceinline__ void flat_pass(const Ray& r, const DModel& m, int w, 
             LdsLeafBuf<K> lb;
             lb.d = &L.lbd[w][0][ln];
             lb.leaf = &L.lbl[w][0][ln];
-            const int32_t n = traverse_pass_wave<K, COUNT>(r, m.inner, lb, bd, bi, ct, q.need);
+            const int32_t n = traverse_pass_wave<K, COUNT, F::LBOX>(r, m.inner, lb, bd, bi, ct, q.need, lbox);
             if (q.need) took(n);
         }
     } else if (q.need) {
@@ -506,7 +511,8 @@ __device__ __forceinline__ void flat_pass(const Ray& r, const DModel& m, int w, 
 template <class F, bool COUNT, int K = kLeafBuf>
 __device__ __forceinline__ void flat_leaf_step(const Ray& r, const DModel& m, int w, int ln, bool live, FlatQ& q,
                                                Ctr& ct, int32_t hyb_a, int32_t hyb_b, const float2_t* pads = nullptr,
-                                               float hv = 0.f, unsigned long long start = kKeyInit) {
+                                               float hv = 0.f, unsigned long long start = kKeyInit,
+                                               const float4_t* lbox = nullptr) {
     static_assert(!F::PADS || F::UO, "the table holds one origin per camera");
     static_assert(!F::WCULL || (F::UO && K >= 2), "the hull is of one origin's directions; sv's LDS slot");
     constexpr bool UO = F::UO, PADS = F::PADS, WCULL = F::WCULL;
@@ -519,6 +525,18 @@ __device__ __forceinline__ void flat_leaf_step(const Ray& r, const DModel& m, in
         cf = cr.x;
         cn = cr.y;
         if constexpr (COUNT) { ct.leaf += 1; ct.cbox += cn; }
+    }
+    // The instrumented build scans every leaf, as the reference does, and runs the leaf test here only
+    // to count: the visits the product pass leaves out (wskip), and in cluster_cands those of their
+    // clusters that pass the table's loose box all the same -- none may.
+    [[maybe_unused]] bool wskip = false;
+    if constexpr (COUNT && F::LBOX) {
+        // (a root that never split is scanned without a pass: never left out)
+        if (live && lbox && !m.root_leaf && isfinite(r.inv.x) && isfinite(r.inv.y) && isfinite(r.inv.z)) {
+            const size_t lf = size_t(uint32_t(L.lbl[w][q.j][ln]));
+            wskip = leaf_box_miss(r, lbox[2 * lf], lbox[2 * lf + 1]);
+            ct.lb_skip += wskip ? 1u : 0u;
+        }
     }
     [[maybe_unused]] uint32_t sv = 0xFFFFFFFFu;  // WCULL: the surviving clusters of the lane's leaf
     if constexpr (WCULL) {
@@ -593,7 +611,7 @@ __device__ __forceinline__ void flat_leaf_step(const Ray& r, const DModel& m, in
                 if constexpr (COUNT && WCULL) ct.ctest += 1;
                 const float bound = __uint_as_float(uint32_t(L.key[w][ln] >> 32));
                 cm = cluster_cands<COUNT, kEarly, PADS>(r, m, c, m.clus[kClusterBlock * size_t(c)],
-                                                m.clus[kClusterBlock * size_t(c) + 1], bound, ct, pads);
+                                                m.clus[kClusterBlock * size_t(c) + 1], bound, ct, pads, wskip);
             }
             cand_rounds<F, COUNT, true, K>(r, m, w, ln, cm, kMaxClusterSize * (cf + ci), ln, ct);
         }
@@ -629,8 +647,10 @@ __device__ __forceinline__ void flat_leaf_step(const Ray& r, const DModel& m, in
         if (valid) {
             if constexpr (COUNT && WCULL) ct.ctest += 1;
             const float bound = __uint_as_float(uint32_t(L.key[w][own] >> 32));
+            bool oskip = false;  // the owner's
+            if constexpr (COUNT && F::LBOX) oskip = __shfl(int(wskip), own) != 0;
             cm = cluster_cands<COUNT, kEarly, PADS>(qr, m, c, m.clus[kClusterBlock * size_t(c)],
-                                                    m.clus[kClusterBlock * size_t(c) + 1], bound, ct, pads);
+                                                    m.clus[kClusterBlock * size_t(c) + 1], bound, ct, pads, oskip);
         }
         cand_rounds<F, COUNT, false, K>(r, m, w, ln, cm, kMaxClusterSize * c, own, ct);
     }
@@ -673,7 +693,8 @@ __device__ __forceinline__ void flat_result(const DModel& m, bool active, int w,
 template <class F, bool COUNT, int K = kLeafBuf>
 __device__ __forceinline__ void flat_query(const Ray& r, const DModel& m, bool active, int w, int ln, int& err, Ctr& ct,
                                            int32_t hyb_a = 0, int32_t hyb_b = 0, const float2_t* pads = nullptr,
-                                           int32_t wcull = 0, unsigned long long start = kKeyInit) {
+                                           int32_t wcull = 0, unsigned long long start = kKeyInit,
+                                           const float4_t* lbox = nullptr) {
     FlatQ q = flat_begin<F, COUNT, K>(r, m, active, w, ln, ct, start);
     // F::WCULL: the direction hull of the lanes that passed the root box, once per query; switched off
     // (wcull == 0, wave-uniform) the hull is unusable and every leaf step keeps all its clusters
@@ -684,10 +705,10 @@ __device__ __forceinline__ void flat_query(const Ray& r, const DModel& m, bool a
     }
     for (;;) {
         ATR_PCLK(uint64_t tc0 = 0; if constexpr (!F::SEED) tc0 = clock64());  // no clocks in an occlusion query
-        flat_pass<F, COUNT, K>(r, m, w, ln, q, err, ct);
+        flat_pass<F, COUNT, K>(r, m, w, ln, q, err, ct, lbox);
         ATR_PCLK(if constexpr (!F::SEED) ct.t_pass += uint32_t(clock64() - tc0));
         if (__ballot(!q.done) == 0) break;
-        flat_leaf_step<F, COUNT, K>(r, m, w, ln, !q.done, q, ct, hyb_a, hyb_b, pads, hv, start);
+        flat_leaf_step<F, COUNT, K>(r, m, w, ln, !q.done, q, ct, hyb_a, hyb_b, pads, hv, start, lbox);
     }
 }
 
@@ -726,11 +747,13 @@ struct SceneHit {
 // clustered scan in flavour F. intersect_models is the models' part; scene_finish (shade.h) the
 // spheres, planes and hit record, so a caller can re-read o and d between the two instead of
 // holding them through the query. pads (FlavPrimaryPads): the camera's row of the table of box
-// growths, one pair per cluster of the scene (model i's from cl_base on); wave-uniform.
+// growths, one pair per cluster of the scene (model i's from cl_base on); wave-uniform. lbox: its row
+// of the table of leaf boxes (model i's from lf_base on), or null.
 template <int SCHED, class F, bool COUNT, int KB = kLeafBuf>
 __device__ __forceinline__ SceneHit intersect_models(const DScene* __restrict__ S, V3 o, V3 d, bool active, int& err,
                                                     Ctr& ct, int32_t hyb_a, int32_t hyb_b,
-                                                    const float2_t* pads = nullptr, int32_t wcull = 0) {
+                                                    const float2_t* pads = nullptr, int32_t wcull = 0,
+                                                    const float4_t* lbox = nullptr) {
     const Ray r = make_ray(o, d);  // renderer.cpp:41-44
     SceneHit sh{kMaxFloat, 0.f, 0.f, 0u, -1};
     const int32_t nmodels = __builtin_amdgcn_readfirstlane(S->nmodels);  // uniform: an SGPR, not a VGPR
@@ -744,9 +767,11 @@ __device__ __forceinline__ SceneHit intersect_models(const DScene* __restrict__ 
             } else {
                 const float2_t* mp = pads;  // the row's entries of this model
                 if constexpr (F::PADS) mp = pads + pads_entry<COUNT>(__builtin_amdgcn_readfirstlane(m.cl_base));
+                const float4_t* ml = lbox;  // and its leaf boxes of this model (two words per leaf)
+                if constexpr (F::LBOX) { if (lbox) ml = lbox + 2 * size_t(__builtin_amdgcn_readfirstlane(m.lf_base)); }
                 const int w = threadIdx.x >> 6, ln = threadIdx.x & 63;
                 ATR_PCLK(uint64_t tcs = clock64());
-                flat_query<F, COUNT, KB>(r, m, active, w, ln, err, ct, hyb_a, hyb_b, mp, wcull);
+                flat_query<F, COUNT, KB>(r, m, active, w, ln, err, ct, hyb_a, hyb_b, mp, wcull, kKeyInit, ml);
                 flat_result<F, COUNT, KB>(m, active, w, ln, h);
                 ATR_PCLK(ct.t_scan += uint32_t(clock64() - tcs));
             }
@@ -771,8 +796,9 @@ __device__ __forceinline__ SceneHit intersect_models(const DScene* __restrict__ 
 template <int SCHED, class F, bool COUNT>
 __device__ __forceinline__ void intersect_scene(const DScene* __restrict__ S, V3 o, V3 d, bool active, Isect& id,
                                                 int& err, Ctr& ct, int32_t hyb_a, int32_t hyb_b,
-                                                const float2_t* pads = nullptr, int32_t wcull = 0) {
-    const SceneHit sh = intersect_models<SCHED, F, COUNT>(S, o, d, active, err, ct, hyb_a, hyb_b, pads, wcull);
+                                                const float2_t* pads = nullptr, int32_t wcull = 0,
+                                                const float4_t* lbox = nullptr) {
+    const SceneHit sh = intersect_models<SCHED, F, COUNT>(S, o, d, active, err, ct, hyb_a, hyb_b, pads, wcull, lbox);
     if (!active) return;
     scene_finish(S, o, d, sh.best, sh.face, sh.fu, sh.fv, sh.nm, id);  // :86-160
 }

@@ -37,6 +37,9 @@ struct Ctr {
     // the facing fold (atr_render_fold_counters): (ray, cluster) pairs that pass the unfolded loose
     // box and fail the table's folded one, and the primitives screened for them
     uint32_t fold_box = 0, fold_screen = 0;
+    // the leaf boxes (atr_render_leaf_box_counters): (lane, leaf) visits whose leaf the product
+    // kernels leave out, and those of them in which a cluster passed the table's loose box (never)
+    uint32_t lb_skip = 0, lb_unsound = 0;
 };
 
 // 1 in the lowest active lane of the wavefront (counts a divergent loop's wave-level iterations)
@@ -374,6 +377,35 @@ __device__ __forceinline__ Inner load_inner_uniform(const float4_t* __restrict__
     return n;
 }
 
+// Flags of a leaf-box entry {LO.xyz, bits(flag)}{HI.xyz, 0} (cluster.h leaf_box_entry builds them).
+constexpr uint32_t kLeafBoxTest = 0u, kLeafBoxEmpty = 1u, kLeafBoxKeep = 2u;
+
+// True when the ray (one of the entry's camera, 1 / d finite on every axis) cannot pass the loose test
+// of any cluster of the leaf: a plain slab test, whatever the best so far. With a kLeafBoxTest entry
+// LO - o and HI - o are finite and so is inv, so no value here is a NaN (a product is at worst
+// infinite); were one to be, the comparisons are false and the leaf is kept.
+__device__ __forceinline__ bool leaf_box_miss(const Ray& r, float4_t e0, float4_t e1) {
+    const uint32_t flag = __float_as_uint(e0.w);
+    if (flag != kLeafBoxTest) return flag == kLeafBoxEmpty;
+    const float x0 = (e0.x - r.o.x) * r.inv.x, x1 = (e1.x - r.o.x) * r.inv.x;
+    const float y0 = (e0.y - r.o.y) * r.inv.y, y1 = (e1.y - r.o.y) * r.inv.y;
+    const float z0 = (e0.z - r.o.z) * r.inv.z, z1 = (e1.z - r.o.z) * r.inv.z;
+    const float tn = fmaxf(fmaxf(fminf(x0, x1), fminf(y0, y1)), fminf(z0, z1));
+    const float tf = fminf(fminf(fmaxf(x0, x1), fmaxf(y0, y1)), fmaxf(z0, z1));
+    return tn > tf || tf < 0.f;
+}
+
+// A leaf-box entry at a wave-uniform address: a 32-byte load from the constant address space -- the
+// table is written by an earlier kernel and read-only for this one's lifetime -- which the compiler
+// issues on the scalar unit, so the box costs no VGPRs.
+typedef float f32x8_t __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ void load_leaf_box_uniform(const float4_t* p, float4_t& e0, float4_t& e1) {
+    using C = const __attribute__((address_space(4))) f32x8_t;
+    const f32x8_t v = *reinterpret_cast<C*>(reinterpret_cast<uint64_t>(p));
+    e0 = float4_t{v[0], v[1], v[2], v[3]};
+    e1 = float4_t{v[4], v[5], v[6], v[7]};
+}
+
 // Examine the children of an inner node (kd_tree.cpp:370-434): box-test children in order
 // until 5 have been hit; inner hits -> returned bit mask, leaf hits -> leaf order buffer.
 // The children boxes are the octants of (lo, v, hi) (kd_tree.cpp:116-148), so every slab
@@ -390,10 +422,17 @@ __device__ __forceinline__ Inner load_inner_uniform(const float4_t* __restrict__
 // no slab value can be NaN, i.e. 1/d is finite on every axis (`cull`, per ray); the rays it
 // helps are bounce rays, whose origins lie inside the tree and whose lines cross boxes behind
 // them (check_ray_AABB_intersection has no t > 0 test, aabb.h:65-93).
-template <int K, bool COUNT, class LB>
+// LBOX (the wave-walked pass of the primary table flavour; the node, and with it the leaf's rank, is
+// wave-uniform): a leaf child that passed the reference's tests and the re-walk bound is inserted only
+// if the lane's ray passes the leaf's box of the camera's row `lbox` (leaf_box_miss: no cluster of the
+// leaf can pass its loose test for this ray, so the leaf's scan would leave the lane's key as it is;
+// DESIGN.md §4b). The child still counts for the 5-hit limit, as in the descent cull, and as there
+// only lanes with finite 1/d take part. The instrumented build inserts every leaf.
+template <int K, bool COUNT, bool LBOX = false, class LB>
 __device__ __forceinline__ uint32_t examine_inner(const Ray& r, const Inner& n, LB& lb,
                                                   int32_t& ncand, float bd, int32_t bi, Ctr& ct,
-                                                  bool first_pass, bool cull = false) {
+                                                  bool first_pass, bool cull = false,
+                                                  const float4_t* lbox = nullptr) {
     const float X0 = (n.lx - r.o.x) * r.inv.x, X1 = (n.vx - r.o.x) * r.inv.x, X2 = (n.hx - r.o.x) * r.inv.x;
     const float Y0 = (n.ly - r.o.y) * r.inv.y, Y1 = (n.vy - r.o.y) * r.inv.y, Y2 = (n.hy - r.o.y) * r.inv.y;
     const float Z0 = (n.lz - r.o.z) * r.inv.z, Z1 = (n.vz - r.o.z) * r.inv.z, Z2 = (n.hz - r.o.z) * r.inv.z;
@@ -434,6 +473,13 @@ __device__ __forceinline__ uint32_t examine_inner(const Ray& r, const Inner& n, 
                 // the static discovery rank orders leaves exactly as this pass discovers them
                 const int32_t id = n.leaf0 + __popc(n.bm & ((1u << i) - 1u) & 0xFFu);
                 if (dis > bd || (dis == bd && id > bi)) {
+                    if constexpr (LBOX && !COUNT) {
+                        if (lbox && cull) {
+                            float4_t e0, e1;
+                            load_leaf_box_uniform(lbox + 2 * size_t(uint32_t(id)), e0, e1);
+                            if (leaf_box_miss(r, e0, e1)) continue;
+                        }
+                    }
                     ++ncand;
                     lb_insert<K>(lb, dis, id);
                 }
@@ -628,9 +674,11 @@ __device__ __forceinline__ int32_t traverse_pass_near(const Ray& r, const float4
 // discovers exactly the leaves -- with the same distances and static ranks -- its lane-private
 // pass discovers, in the same order. Called by every lane of the wave (converged); `part` = this
 // lane runs a pass. Returns the lane's candidate count (-1: tree deeper than the mask stack).
-template <int K, bool COUNT, class LB>
+// LBOX, lbox: examine_inner's leaf boxes, the camera's row at this model's first leaf (wave-uniform; null: off).
+template <int K, bool COUNT, bool LBOX = false, class LB>
 __device__ __forceinline__ int32_t traverse_pass_wave(const Ray& r, const float4_t* __restrict__ tab, LB& lb,
-                                                      float bd, int32_t bi, Ctr& ct, bool part) {
+                                                      float bd, int32_t bi, Ctr& ct, bool part,
+                                                      const float4_t* lbox = nullptr) {
     const bool first_pass = bi < 0;
     if constexpr (COUNT) { if (part) ct.pass += 1; }
     if (part) lb_clear<K>(lb);
@@ -641,7 +689,8 @@ __device__ __forceinline__ int32_t traverse_pass_wave(const Ray& r, const float4
     const bool cull = isfinite(r.inv.x) && isfinite(r.inv.y) && isfinite(r.inv.z);
 #endif
     Inner cur = load_inner_uniform(tab, 0);
-    uint64_t lo = part ? uint64_t(examine_inner<K, COUNT>(r, cur, lb, ncand, bd, bi, ct, first_pass, cull)) : 0;
+    uint64_t lo = 0;
+    if (part) lo = examine_inner<K, COUNT, LBOX>(r, cur, lb, ncand, bd, bi, ct, first_pass, cull, lbox);
     uint64_t hi = 0;
     uint32_t bm = cur.bm;  // wave-uniform walk state
     int32_t parent = -1, lvl = 0;
@@ -658,7 +707,8 @@ __device__ __forceinline__ int32_t traverse_pass_wave(const Ray& r, const float4
             const uint32_t innerm = ~bm & ((1u << s) - 1u);
             const int32_t id = int32_t(bm >> 8) + __popc(innerm);
             cur = load_inner_uniform(tab, id);
-            const uint64_t cm = act ? uint64_t(examine_inner<K, COUNT>(r, cur, lb, ncand, bd, bi, ct, first_pass, cull)) : 0;
+            uint64_t cm = 0;
+            if (act) cm = examine_inner<K, COUNT, LBOX>(r, cur, lb, ncand, bd, bi, ct, first_pass, cull, lbox);
             ++lvl;
             if (lvl >= kMaskLevels) return -1;
             if (lvl < 8) lo |= cm << (8 * lvl);

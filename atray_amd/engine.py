@@ -162,6 +162,7 @@ EXPORTS = [
     "atr_trace_rays", "atr_occluded_rays", "atr_gather_occlusion", "atr_gather_directions",
     "atr_radiance_rays", "atr_gather_radiance", "atr_mesh_texels", "atr_texels_to_image",
     "atr_render_fold_counters", "atr_camera_pads_row", "atr_default_denoise_params", "atr_denoise",
+    "atr_render_leaf_box_counters", "atr_camera_leaf_boxes_row",
 ]
 # the diagnostic build's extra symbols (include/atray_diag.h; make -C atray_amd/csrc DIAG=1)
 DIAG_EXPORTS = ["atr_render_wave_trace", "atr_render_phase_clocks", "atr_render_path_counters",
@@ -233,6 +234,8 @@ def lib():
         "atr_render_cull_counters": ([vp, P(atr_camera), vp, i32, C.c_uint64, i32, i64 * 5], C.c_int),
         "atr_render_fold_counters": ([vp, P(atr_camera), vp, i32, C.c_uint64, i32, i64 * 2], C.c_int),
         "atr_camera_pads_row": ([vp, C.c_float * 3, vp, vp, vp, i64], i64),
+        "atr_render_leaf_box_counters": ([vp, P(atr_camera), vp, i32, C.c_uint64, i32, i64 * 2], C.c_int),
+        "atr_camera_leaf_boxes_row": ([vp, C.c_float * 3, vp, vp, i64], i64),
         "atr_render_tile_costs": ([vp, P(atr_camera), vp, i32, C.c_uint64, vp], C.c_int),
         "atr_render_wave_trace": ([vp, P(atr_camera), vp, i32, C.c_uint64, i32, vp, i64, P(i64)], C.c_int),
         "atr_packed_pixel_map": ([vp, i32, i32, i32, vp, i64], i64),
@@ -1155,6 +1158,29 @@ class Engine:
             check(min(int(lib().atr_camera_pads_row(self.h, e, row.ctypes.data, boxes.ctypes.data,
                                                     edges.ctypes.data, n)), 0), "camera pads row")
         return row, boxes, edges
+
+    def leaf_box_counters(self, cam, tiles, seed, variant=ATR_KERNEL_AUTO):
+        """The primary kernels' leaf boxes in one instrumented render (atr_render_leaf_box_counters):
+        (ray, leaf) visits the product passes leave out, and the unsound ones among them (always 0)."""
+        arr, n = tiles if isinstance(tiles, tuple) else tiles_array(tiles)
+        out = (C.c_int64 * 2)()
+        check(lib().atr_render_leaf_box_counters(self.h, C.byref(cam), C.cast(arr, C.c_void_p), n,
+                                                 C.c_uint64(seed & (2**64 - 1)), int(variant), out), "leaf box counters")
+        return {"skipped_visits": int(out[0]), "unsound_skips": int(out[1])}
+
+    def camera_leaf_boxes_row(self, eye):
+        """The row of the table of leaf boxes that a one-camera launch at `eye` reads, built by the launch's
+        own table kernels (atr_camera_leaf_boxes_row), per scene leaf: lo (n, 3) f32, hi (n, 3) f32,
+        flag (n,) u32 (0 test, 1 no clusters, 2 never left out), ranges (n, 2) i32 = the leaf's first
+        cluster in camera_pads_row's numbering and its cluster count."""
+        e = (C.c_float * 3)(*[float(x) for x in eye])
+        n = int(lib().atr_camera_leaf_boxes_row(self.h, e, None, None, 0))
+        check(min(n, 0), "camera leaf boxes row")
+        row, ranges = np.zeros((n, 8), np.float32), np.zeros((n, 2), np.int32)
+        if n:
+            check(min(int(lib().atr_camera_leaf_boxes_row(self.h, e, row.ctypes.data, ranges.ctypes.data, n)), 0),
+                  "camera leaf boxes row")
+        return row[:, 0:3].copy(), row[:, 4:7].copy(), row[:, 3].copy().view(np.uint32), ranges
 
     def tile_costs(self, cam, tiles, seed):
         """Shader clocks spent per tile by one render of `tiles` (load-balance calibration)."""

@@ -42,7 +42,7 @@ enum {
                                status or a count: std::bad_alloc comes back as this, anything else as
                                ATR_E_INVALID -- from the count-returning ones (atr_make_tiles,
                                atr_make_shard_tiles, atr_balance_shard_tiles, atr_render_packed_size,
-                               atr_packed_pixel_map, atr_camera_pads_row), whose results are never
+                               atr_packed_pixel_map, atr_camera_pads_row, atr_camera_leaf_boxes_row), whose results are never
                                negative, as that negative value */
     ATR_E_NOSCENE = -4,     /* render before atr_scene_upload */
     ATR_E_TREE_DEPTH = -5,  /* octree deeper than the traversal's mask stack (16 levels) */
@@ -179,7 +179,10 @@ typedef struct atr_ctx atr_ctx;
    And a second one: ATR_WAVE_CULL=0 makes them test every cluster of a leaf per ray instead of
    first culling the leaf's clusters against the wave's direction hull; same bits.
    And a third: ATR_FACING_FOLD=0 leaves the table's loose growths unfolded, sized for the smallest
-   det the culled test accepts instead of the camera's det floor per cluster; same bits. */
+   det the culled test accepts instead of the camera's det floor per cluster; same bits.
+   And a fourth: ATR_LEAF_BOX=0 builds no per-camera table of leaf boxes, so the primary passes insert
+   every leaf the reference scans instead of leaving out those whose grown content the ray misses
+   (DESIGN.md 4b); same bits. */
 int atr_create(int device, atr_ctx** out);
 int atr_destroy(atr_ctx* ctx);
 const char* atr_version(void);
@@ -414,6 +417,22 @@ int atr_render_fold_counters(atr_ctx* ctx, const atr_camera* cam, const atr_tile
    0, 0}; edges (may be NULL), 96 f32 per cluster = ab.xyz, ac.xyz of its 16 primitive slots, 0 past
    its count. */
 int64_t atr_camera_pads_row(atr_ctx* ctx, const float eye[3], float* row, float* boxes, float* edges, int64_t cap);
+/* Diagnostic, synchronous: the same instrumented render's counters of the primary kernels' leaf boxes
+   (DESIGN.md §4b). The instrumented render scans every leaf; it runs the leaf test only to count
+   [0] the (ray, leaf) visits whose leaf the product kernels' passes leave out, and [1] those of them in
+   which a cluster passed the table's loose box all the same -- always 0. Both 0 with ATR_LEAF_BOX=0 or
+   ATR_CAMERA_PADS=0 and for every kernel without the table. */
+int atr_render_leaf_box_counters(atr_ctx* ctx, const atr_camera* cam, const atr_tile* tiles, int32_t ntiles,
+                                 uint64_t seed, int32_t variant, int64_t counters_out[2]);
+/* Diagnostic, synchronous: the row of the table of leaf boxes that a one-camera launch of this context
+   at `eye` reads, built as the launch builds it (the row of box growths of atr_camera_pads_row, then
+   the boxes from it), whether or not ATR_LEAF_BOX switched the table off. Returns the scene's leaf
+   count n -- the leaves of its tree models in model order, each model's by discovery rank -- or an
+   error < 0; with row == NULL or cap < n nothing else is done. row: 8 f32 per leaf = {LO.xyz,
+   bits(flag)}{HI.xyz, 0}; flag 0: a ray from the eye that misses [LO, HI] passes no cluster of the leaf,
+   1: a leaf without clusters, 2: never left out (a non-finite operand). ranges (may be NULL): 2 int32
+   per leaf = its first cluster in atr_camera_pads_row's numbering and its cluster count. */
+int64_t atr_camera_leaf_boxes_row(atr_ctx* ctx, const float eye[3], float* row, int32_t* ranges, int64_t cap);
 /* Number of pixels a PACKED render of these tiles writes. */
 int64_t atr_render_packed_size(const atr_tile* tiles, int32_t ntiles);
 /* Host-only: pixel index (y * width + x) of every slot of a PACKED render of these tiles, in
