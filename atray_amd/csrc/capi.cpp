@@ -296,6 +296,10 @@ struct atr_ctx {
     bool wave_cull = true;
     // ATR_LEAF_BOX at atr_create (0 = no table of leaf boxes: the primary passes insert every leaf)
     bool leaf_box = true;
+    // ATR_SKY_PATH at atr_create (0 = every wave of the primary kernels walks the scene), and the
+    // scene's record for that path (engine.h SkyRecord; atr_scene_upload fills it, `on` included)
+    bool sky_path = true;
+    SkyRecord sky = {};
     // Ray queries' workspace (atr_trace_rays, query.hip), apart from the path workspaces and grow-only:
     // `rays` = {key, rank} and the key order for `cap` rays (12 B each; sorted batches only) and, in
     // its first 256 B, the head counter; `bins` = `nbins` arrival counters (zero between calls: the
@@ -343,6 +347,7 @@ void apply_tuning(const atr_ctx* c, RenderParams& P) {
     P.hyb_a = c->tune.hybrid_a;
     P.hyb_b = c->tune.hybrid_b;
     P.wave_cull = c->wave_cull ? 1 : 0;
+    P.sky = c->sky;
 }
 
 int dev_upload(atr_ctx* c, const void* src, size_t bytes, void** out) {
@@ -360,6 +365,39 @@ int dev_upload(atr_ctx* c, const void* src, size_t bytes, void** out) {
     c->scene_bytes += int64_t(b.n);
     *out = b.p;
     return ATR_OK;
+}
+
+// The sky path's record of a scene (engine.h SkyRecord; render.hip) from an upload's inputs and its
+// packed trees (packed[i] of a tree model, as pack_tree left it): per model the six floats its query
+// starts with as the device tables hold them -- nodes[0]'s bounds of a tree model (scan.h flat_begin:
+// box_check), the surrounding_aabb copied into DModel::aabb of a brute-force one (scan.h
+// intersect_models: box_entry) -- and what shade.h scene_finish leaves for a ray that hits no model
+// when there is no sphere and no plane: type T_SKY, so material 0's emission, face kSkyFace, and t =
+// the kMaxFloat that intersect_models' SceneHit starts from. on = 0, and no box recorded, with more
+// models than the record holds or with any sphere or plane.
+void sky_record(const atr_material* mats, const atr_model* models, int32_t nmodels, int32_t nspheres,
+                int32_t nplanes, const std::vector<PackedTree>& packed, SkyRecord& sky) {
+    sky = SkyRecord{};
+    sky.on = nmodels <= kSkyBoxes && nspheres == 0 && nplanes == 0 ? 1 : 0;
+    sky.face = kSkyFace;
+    sky.t = kMaxFloat;
+    sky.em[0] = mats[0].emission.x, sky.em[1] = mats[0].emission.y, sky.em[2] = mats[0].emission.z;
+    if (!sky.on) return;
+    sky.n = nmodels;
+    for (int32_t i = 0; i < nmodels; ++i) {
+        if (models[i].tree) {
+            if (packed[size_t(i)].nodes.empty()) {  // no root to test: every wave walks the scene
+                sky.on = sky.n = 0;
+                return;
+            }
+            const DNode& r = packed[size_t(i)].nodes[0];
+            const float b[6] = {r.lo_x, r.lo_y, r.lo_z, r.hi_x, r.hi_y, r.hi_z};
+            std::memcpy(sky.box[i], b, sizeof(b));
+        } else {
+            std::memcpy(sky.box[i], models[i].surrounding_aabb, sizeof(sky.box[i]));
+            sky.brute |= 1u << i;
+        }
+    }
 }
 
 // A mesh's per-face shading record (renderer.cpp:124-149; DModel::shade, read by shade.h's
@@ -1362,6 +1400,9 @@ int atr_create(int device, atr_ctx** out) try {
     // ATR_LEAF_BOX=0: this context builds no table of leaf boxes and its primary passes insert every
     // leaf (A/B runs and tests; same output bits either way)
     if (const char* v = std::getenv("ATR_LEAF_BOX")) c->leaf_box = !(v[0] == '0' && v[1] == '\0');
+    // ATR_SKY_PATH=0: no wave of this context's primary kernels takes the sky path (render.hip); the
+    // same kernels, and the same output bits either way.
+    if (const char* v = std::getenv("ATR_SKY_PATH")) c->sky_path = !(v[0] == '0' && v[1] == '\0');
     const int rc = [&]() -> int {  // any failure below releases what was created (atr_destroy)
         HIPCHK(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
         HIPCHK(hipEventCreate(&c->ev_start));
@@ -1497,10 +1538,13 @@ int atr_scene_upload(atr_ctx* c, const atr_material* mats, int32_t nmats, const 
                 if (vi < 0 || size_t(vi) >= M.vertices.size()) return ATR_E_INVALID;
         }
     }
+    SkyRecord sky;  // from the packed trees, before the loop below takes them apart
+    sky_record(mats, models, nmodels, nspheres, nplanes, packed, sky);
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(wait_all(c));  // kernels on any stream may still read the old scene
     free_scene(c);
     ++c->scene_gen;  // every table of box growths belongs to the old scene now
+    c->sky = SkyRecord{};  // the new scene's at the end of a successful upload alone
     DScene S;
     std::memset(&S, 0, sizeof(S));
     for (int32_t i = 0; i < nmats; ++i) {
@@ -1629,6 +1673,8 @@ int atr_scene_upload(atr_ctx* c, const atr_material* mats, int32_t nmats, const 
         c->d_scene = static_cast<DScene*>(p);
     }
     c->nmodels = nmodels;
+    if (!c->sky_path) sky.on = 0;
+    c->sky = sky;
     return ATR_OK;
 } ATR_ABI_CATCH
 
@@ -2374,7 +2420,8 @@ int atr_render_wave_trace(atr_ctx* c, const atr_camera* cam, const atr_tile* til
     P.wave_trace = static_cast<unsigned long long*>(tr.p);
     apply_tuning(c, P);
     const int ts = sched_of(variant);  // per-cell trace: 8x8-cell schedules only
-    HIPCHK(atr_launch_render(P, ts < 0 || ts == kSchedPaths ? 7 : ts, 0, nullptr));
+    // through launch_kernels, as a product launch goes: HYBRID's primaries read the camera's table
+    HIPCHK(launch_kernels(c, P, ts < 0 || ts == kSchedPaths ? 7 : ts, nullptr));
     HIPCHK(hipDeviceSynchronize());
     if (nb) HIPCHK(hipMemcpy(out, tr.p, 3 * nb * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return ATR_OK;
@@ -2384,7 +2431,7 @@ int atr_render_wave_trace(atr_ctx* c, const atr_camera* cam, const atr_tile* til
 
 // One instrumented (COUNT) render; h = the 16 device counters (render.hip: [0..9] work counters,
 // [10..15] phase clocks, zero unless built with -DATR_PHASE_CLOCKS).
-constexpr int kCounterSlots = 34;
+constexpr int kCounterSlots = 35;
 static int count_launch(atr_ctx* c, const atr_camera* cam, const atr_tile* tiles, int32_t ntiles, uint64_t seed,
                         int32_t variant, unsigned long long h[kCounterSlots]) {
     if (!c || !cam || ntiles < 0 || (ntiles && !tiles)) return ATR_E_INVALID;
@@ -2461,6 +2508,47 @@ int atr_render_leaf_box_counters(atr_ctx* c, const atr_camera* cam, const atr_ti
     if (rc != ATR_OK) return rc;
     out[0] = int64_t(h[32]);  // (lane, leaf) visits whose leaf the product passes leave out
     out[1] = int64_t(h[33]);  // those of them in which a cluster passed the table's loose box
+    return ATR_OK;
+} ATR_ABI_CATCH
+
+int atr_render_sky_cells(atr_ctx* c, const atr_camera* cam, const atr_tile* tiles, int32_t ntiles, uint64_t seed,
+                         int32_t variant, int64_t* out) try {
+    if (!out) return ATR_E_INVALID;
+    unsigned long long h[kCounterSlots];
+    const int rc = count_launch(c, cam, tiles, ntiles, seed, variant, h);
+    if (rc != ATR_OK) return rc;
+    *out = int64_t(h[34]);  // waves whose active lanes all fail every model's first test
+    return ATR_OK;
+} ATR_ABI_CATCH
+
+static void sky_record_out(const SkyRecord& sky, int32_t info[4], float values[28]) {
+    info[0] = sky.on, info[1] = sky.n, info[2] = int32_t(sky.brute), info[3] = int32_t(sky.face);
+    values[0] = sky.t;
+    std::memcpy(values + 1, sky.em, sizeof(sky.em));
+    std::memcpy(values + 4, sky.box, sizeof(sky.box));
+}
+
+int atr_scene_sky_record(atr_ctx* c, int32_t info[4], float values[28]) try {
+    if (!c || !info || !values) return ATR_E_INVALID;
+    if (!c->d_scene) return ATR_E_NOSCENE;
+    sky_record_out(c->sky, info, values);
+    return ATR_OK;
+} ATR_ABI_CATCH
+
+int atr_sky_record_host(const atr_material* mats, int32_t nmats, const atr_model* models, int32_t nmodels,
+                        int32_t nspheres, int32_t nplanes, int32_t info[4], float values[28]) try {
+    if (!mats || nmats <= 0 || nmats > kMaxMaterials || nmodels < 0 || nmodels > kMaxModels || (nmodels && !models) ||
+        nspheres < 0 || nplanes < 0 || !info || !values)
+        return ATR_E_INVALID;
+    std::vector<PackedTree> packed(size_t(nmodels), PackedTree{});
+    for (int32_t i = 0; i < nmodels; ++i) {
+        if (!models[i].mesh) return ATR_E_INVALID;
+        if (!models[i].tree) continue;
+        if (const int rc = pack_tree(models[i].tree->t, default_tuning().cluster_size, packed[size_t(i)])) return rc;
+    }
+    SkyRecord sky;
+    sky_record(mats, models, nmodels, nspheres, nplanes, packed, sky);
+    sky_record_out(sky, info, values);
     return ATR_OK;
 } ATR_ABI_CATCH
 

@@ -177,6 +177,24 @@ constexpr int32_t kBlockPrio = 1;
 constexpr int kPlanClassShift = 4;
 constexpr uint8_t kPlanClassMask = 0x70, kPlanPrio = 0x80;
 
+// What a ray that passes no model's first test gets, and those tests' operands, as the kernels load
+// them (capi.cpp atr_scene_upload): box i = the six floats model i's query starts with -- a tree
+// model's nodes[0] bounds for box_check (scan.h flat_begin), a brute-force model's aabb for box_entry
+// (scan.h intersect_models; bit i of `brute`), lo.xyz then hi.xyz -- and the record scene_finish
+// (shade.h) leaves for no model hit in a scene without spheres and planes: the emission of material
+// 0, face, t. on: the path is usable (n <= kSkyBoxes models, no sphere, no plane, not switched off).
+constexpr int kSkyBoxes = 4;
+constexpr uint32_t kSkyFace = 0xFFFFFFFFu;  // shade.h scene_finish: id.face of a hit that is no triangle
+struct SkyRecord {
+    int32_t on;
+    int32_t n;
+    uint32_t brute;
+    uint32_t face;
+    float t;
+    float em[3];
+    float box[kSkyBoxes][6];
+};
+
 // Per-render kernel argument (by value, no dynamic indexing into it).
 struct RenderParams {
     atr_camera cam;
@@ -228,6 +246,12 @@ struct RenderParams {
     // read by the kernels that read pads only; same output bits either way.
     const float4_t* lbox;
     int32_t lbox_stride;
+    // HYBRID's primary kernels' sky path (render.hip): the scene's record of every
+    // model's first test (SkyRecord below, filled at upload), by value. sky.on != 0: a wave none of
+    // whose active lanes passes any of the sky.n tests writes the sky's outputs from this record and
+    // reads nothing of the scene. Last in the struct and read by those kernels only; same output bits
+    // either way.
+    SkyRecord sky;
 };
 
 // The eyes of a launch's cameras, by value, for the kernel that fills the table.

@@ -169,28 +169,64 @@ __global__ __launch_bounds__(256, OCC) void render_kernel(RenderParams P) {
     V3 dir = mk(0.f, 0.f, 1.f);
     if (!cm.anti_aliasing) dir = unit(sub(add(add(fc, scale(cx, film_x)), scale(cy, film_y)), eye));  // :350-351
     if constexpr (PRIMARY) {
-        Isect id;
-        id.type = T_NONE;
-        if constexpr (PADS) {
-            // the camera's row: the frame index and the stride are wave-uniform, the base stays in SGPRs
-            const int32_t row = P.nfcam > 0 ? __builtin_amdgcn_readfirstlane(fidx) : 0;
-            const float2_t* pads = uniform_global(P.pads) + pads_entry<COUNT>(size_t(int64_t(row) * P.pads_stride));
-            // and its row of leaf boxes (null: switched off, or no table)
-            const float4_t* lbox = uniform_global(P.lbox);
-            if (lbox) lbox += 2 * size_t(int64_t(row) * P.lbox_stride);
-            intersect_scene<SCHED, FlavPrimaryPads, COUNT>(S, eye, dir, active, id, err, ct, P.hyb_a, P.hyb_b, pads,
-                                                           P.wave_cull, lbox);
-        } else {
-            intersect_scene<SCHED, FlavPrimary, COUNT>(S, eye, dir, active, id, err, ct, P.hyb_a, P.hyb_b, nullptr,
-                                                       P.wave_cull);
+        // The sky path (HYBRID): every model's query starts with one box test of the
+        // ray (flat_begin's box_check of nodes[0], intersect_models' box_entry of a brute-force
+        // model's aabb), and a lane that fails them all gets scene_finish's sky record when the scene
+        // has no sphere and no plane. P.sky holds those tests' operands and that record. A wave none
+        // of whose active lanes passes any test -- the same functions on the same bits as the slow
+        // path would run -- writes the record and reads nothing of the scene. The instrumented build
+        // only counts such waves (counters[34]) and walks the scene as ever.
+        [[maybe_unused]] bool sky = false;
+        if constexpr (SCHED == SCHED_HYBRID) {
+            if (P.sky.on) {
+                const Ray r = make_ray(eye, dir);
+                bool any = false;
+#pragma unroll
+                for (int i = 0; i < kSkyBoxes; ++i) {
+                    if (i < P.sky.n) {
+                        const float* q = P.sky.box[i];
+                        if ((P.sky.brute >> i) & 1u) any = any || box_entry(r, q[0], q[1], q[2], q[3], q[4], q[5]) != 0;
+                        else any = any || box_check(r, q[0], q[1], q[2], q[3], q[4], q[5]);
+                    }
+                }
+                sky = __ballot(active && any) == 0;
+            }
         }
-        if (active) {
-            const DMaterial& mat = S->mats[id.material];
-            col = add(col, mk(mat.ex, mat.ey, mat.ez));  // ret = (0 + (1,1,1) x emission)
-            hit_face = id.face;
-            hit_t = id.t;
-            casts = id.type == T_SKY ? 0u : 1u;
-            traced = 1;
+        if (!COUNT && sky) {
+            if (active) {
+                col = add(col, mk(P.sky.em[0], P.sky.em[1], P.sky.em[2]));
+                hit_face = P.sky.face;
+                hit_t = P.sky.t;
+                casts = 0u;
+                traced = 1;
+            }
+        } else {
+            Isect id;
+            id.type = T_NONE;
+            if constexpr (PADS) {
+                // the camera's row: the frame index and the stride are wave-uniform, the base stays in SGPRs
+                const int32_t row = P.nfcam > 0 ? __builtin_amdgcn_readfirstlane(fidx) : 0;
+                const float2_t* pads = uniform_global(P.pads) + pads_entry<COUNT>(size_t(int64_t(row) * P.pads_stride));
+                // and its row of leaf boxes (null: switched off, or no table)
+                const float4_t* lbox = uniform_global(P.lbox);
+                if (lbox) lbox += 2 * size_t(int64_t(row) * P.lbox_stride);
+                intersect_scene<SCHED, FlavPrimaryPads, COUNT>(S, eye, dir, active, id, err, ct, P.hyb_a, P.hyb_b, pads,
+                                                               P.wave_cull, lbox);
+            } else {
+                intersect_scene<SCHED, FlavPrimary, COUNT>(S, eye, dir, active, id, err, ct, P.hyb_a, P.hyb_b, nullptr,
+                                                           P.wave_cull);
+            }
+            if (active) {
+                const DMaterial& mat = S->mats[id.material];
+                col = add(col, mk(mat.ex, mat.ey, mat.ez));  // ret = (0 + (1,1,1) x emission)
+                hit_face = id.face;
+                hit_t = id.t;
+                casts = id.type == T_SKY ? 0u : 1u;
+                traced = 1;
+            }
+        }
+        if constexpr (COUNT && SCHED == SCHED_HYBRID) {
+            if (sky && lane == 0) atomicAdd(P.counters + 34, 1ull);
         }
     } else {
         for (uint32_t s = 0; s < cm.samples_per_pixel; ++s) {
@@ -331,6 +367,7 @@ __global__ __launch_bounds__(256, OCC) void render_kernel(RenderParams P) {
                 if (lane == 0 && x2) atomicAdd(C + 32 + k, (unsigned long long)x2);
             }
         }
+        // counters[34] (HYBRID's primaries): the waves the product kernels' sky path takes, added above
         // counters[10..15]: wave clocks in DFS passes, lane-private scans, dealt rounds, whole
         // wave, per-step preparation, whole FLAT/HYBRID scan (phases: diagnostic build only)
         if (lane == 0) {

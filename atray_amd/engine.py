@@ -163,6 +163,7 @@ EXPORTS = [
     "atr_radiance_rays", "atr_gather_radiance", "atr_mesh_texels", "atr_texels_to_image",
     "atr_render_fold_counters", "atr_camera_pads_row", "atr_default_denoise_params", "atr_denoise",
     "atr_render_leaf_box_counters", "atr_camera_leaf_boxes_row",
+    "atr_render_sky_cells", "atr_scene_sky_record", "atr_sky_record_host",
 ]
 # the diagnostic build's extra symbols (include/atray_diag.h; make -C atray_amd/csrc DIAG=1)
 DIAG_EXPORTS = ["atr_render_wave_trace", "atr_render_phase_clocks", "atr_render_path_counters",
@@ -236,6 +237,9 @@ def lib():
         "atr_camera_pads_row": ([vp, C.c_float * 3, vp, vp, vp, i64], i64),
         "atr_render_leaf_box_counters": ([vp, P(atr_camera), vp, i32, C.c_uint64, i32, i64 * 2], C.c_int),
         "atr_camera_leaf_boxes_row": ([vp, C.c_float * 3, vp, vp, i64], i64),
+        "atr_render_sky_cells": ([vp, P(atr_camera), vp, i32, C.c_uint64, i32, P(i64)], C.c_int),
+        "atr_scene_sky_record": ([vp, i32 * 4, C.c_float * 28], C.c_int),
+        "atr_sky_record_host": ([vp, i32, vp, i32, i32, i32, i32 * 4, C.c_float * 28], C.c_int),
         "atr_render_tile_costs": ([vp, P(atr_camera), vp, i32, C.c_uint64, vp], C.c_int),
         "atr_render_wave_trace": ([vp, P(atr_camera), vp, i32, C.c_uint64, i32, vp, i64, P(i64)], C.c_int),
         "atr_packed_pixel_map": ([vp, i32, i32, i32, vp, i64], i64),
@@ -295,6 +299,29 @@ def signatures():
 
 def vec3(t):
     return atr_vec3(float(t[0]), float(t[1]), float(t[2]))
+
+
+def _sky_record(info, vals):
+    v = np.array(list(vals), np.float32)
+    return {"on": int(info[0]), "n": int(info[1]), "brute": int(info[2]) & 0xFFFFFFFF, "face": int(info[3]) & 0xFFFFFFFF,
+            "t": v[0:1].copy(), "emission": v[1:4].copy(), "boxes": v[4:28].reshape(4, 6).copy()}
+
+
+def sky_record(materials, models, nspheres=0, nplanes=0):
+    """The sky path's record of a scene from upload()'s arguments, on the host (atr_sky_record_host):
+    on, n, brute (bit per model), face, t (1,) f32, emission (3,) f32, boxes (4, 6) f32 = lo.xyz, hi.xyz."""
+    mats = (atr_material * len(materials))(*[atr_material(vec3(e), vec3(r), float(s)) for e, r, s in materials])
+    mods = (atr_model * max(1, len(models)))()
+    for i, (mesh, tree, aabb, mat) in enumerate(models):
+        mods[i].mesh = mesh.h.value
+        mods[i].tree = tree.h.value if tree is not None else None
+        for k in range(6):
+            mods[i].surrounding_aabb[k] = float(aabb[k])
+        mods[i].material = int(mat)
+    info, vals = (C.c_int32 * 4)(), (C.c_float * 28)()
+    check(lib().atr_sky_record_host(C.cast(mats, C.c_void_p), len(materials), C.cast(mods, C.c_void_p), len(models),
+                                    int(nspheres), int(nplanes), info, vals), "sky record")
+    return _sky_record(info, vals)
 
 
 def tiles_array(tiles):
@@ -1167,6 +1194,21 @@ class Engine:
         check(lib().atr_render_leaf_box_counters(self.h, C.byref(cam), C.cast(arr, C.c_void_p), n,
                                                  C.c_uint64(seed & (2**64 - 1)), int(variant), out), "leaf box counters")
         return {"skipped_visits": int(out[0]), "unsound_skips": int(out[1])}
+
+    def sky_cells(self, cam, tiles, seed, variant=ATR_KERNEL_AUTO):
+        """The wavefronts of one instrumented render none of whose rays passes any model's first box test
+        (atr_render_sky_cells): the ones the product kernels finish without reading the scene."""
+        arr, n = tiles if isinstance(tiles, tuple) else tiles_array(tiles)
+        out = C.c_int64()
+        check(lib().atr_render_sky_cells(self.h, C.byref(cam), C.cast(arr, C.c_void_p), n,
+                                         C.c_uint64(seed & (2**64 - 1)), int(variant), C.byref(out)), "sky cells")
+        return int(out.value)
+
+    def sky_record(self):
+        """What the sky path's kernels get of the uploaded scene (atr_scene_sky_record); see sky_record()."""
+        info, vals = (C.c_int32 * 4)(), (C.c_float * 28)()
+        check(lib().atr_scene_sky_record(self.h, info, vals), "sky record")
+        return _sky_record(info, vals)
 
     def camera_leaf_boxes_row(self, eye):
         """The row of the table of leaf boxes that a one-camera launch at `eye` reads, built by the launch's

@@ -182,7 +182,9 @@ typedef struct atr_ctx atr_ctx;
    det the culled test accepts instead of the camera's det floor per cluster; same bits.
    And a fourth: ATR_LEAF_BOX=0 builds no per-camera table of leaf boxes, so the primary passes insert
    every leaf the reference scans instead of leaving out those whose grown content the ray misses
-   (DESIGN.md 4b); same bits. */
+   (DESIGN.md 4b); same bits.
+   And a fifth: ATR_SKY_PATH=0 makes every wavefront of the primary-only kernels walk the scene, also
+   those none of whose rays passes any model's first box test; same bits. */
 int atr_create(int device, atr_ctx** out);
 int atr_destroy(atr_ctx* ctx);
 const char* atr_version(void);
@@ -424,6 +426,24 @@ int64_t atr_camera_pads_row(atr_ctx* ctx, const float eye[3], float* row, float*
    ATR_CAMERA_PADS=0 and for every kernel without the table. */
 int atr_render_leaf_box_counters(atr_ctx* ctx, const atr_camera* cam, const atr_tile* tiles, int32_t ntiles,
                                  uint64_t seed, int32_t variant, int64_t counters_out[2]);
+/* Diagnostic, synchronous: the same instrumented render's count of the primary kernels' sky cells
+   (DESIGN.md §4a): the wavefronts (8x8 cells, or parts of split cells) none of whose pixels' rays passes
+   the first box test of any model, which the product kernels finish from their arguments without
+   reading the scene. The instrumented render walks the scene for them as for every other wavefront and
+   only counts them. 0 with ATR_SKY_PATH=0, in a scene with a sphere, a plane or more than 4 models,
+   and for every kernel without the path (LANE, every launch that is not primary-only). */
+int atr_render_sky_cells(atr_ctx* ctx, const atr_camera* cam, const atr_tile* tiles, int32_t ntiles,
+                         uint64_t seed, int32_t variant, int64_t* cells_out);
+/* Diagnostic, host-only: what the sky path's kernels get of the uploaded scene, as they load it.
+   info = {path usable (0 with ATR_SKY_PATH=0, a sphere, a plane or more than 4 models), models
+   recorded, bit i set: model i is brute force and its box is tested as its surrounding_aabb is (else
+   the root node's bounds of its tree), the hit_face of a sky pixel}; values = {the hit_t of a sky
+   pixel, the sky's emission (3), then 6 floats per model slot (4 slots): lo.xyz, hi.xyz of the box
+   its query starts with, 0 past the models recorded}. atr_sky_record_host computes the same record
+   from an upload's arguments without a context or a device (and so without ATR_SKY_PATH). */
+int atr_scene_sky_record(atr_ctx* ctx, int32_t info[4], float values[28]);
+int atr_sky_record_host(const atr_material* mats, int32_t nmats, const atr_model* models, int32_t nmodels,
+                        int32_t nspheres, int32_t nplanes, int32_t info[4], float values[28]);
 /* Diagnostic, synchronous: the row of the table of leaf boxes that a one-camera launch of this context
    at `eye` reads, built as the launch builds it (the row of box growths of atr_camera_pads_row, then
    the boxes from it), whether or not ATR_LEAF_BOX switched the table off. Returns the scene's leaf

@@ -32,7 +32,14 @@ int atr_render_simd_counters(atr_ctx* ctx, const atr_camera* cam, const atr_tile
                              uint64_t seed, int32_t variant, int64_t out[7]);
 /* Diagnostic: one render of `tiles` recording, per 8x8 work block (block order), the wave's start
    and end on the 100 MHz device clock and its HW_ID | XCC_ID << 32. out = 3 u64 per block;
-   with out == NULL (or cap too small) only *nblocks is set. */
+   with out == NULL (or cap too small) only *nblocks is set. The launch goes the product's way:
+   HYBRID's primary kernels read the camera's table and take the sky path (4a) unless
+   the context was created with their switches off.
+   The instrumented render's device counters (render.hip; the product library's atr_render_*counters
+   entry points of atray.h read them): [0..9] work, [10..15] phase clocks, [16..21] bounce-loop lane
+   use, [22..26] SIMD efficiency, [27..29] wave cull, [30..31] facing fold, [32..33] leaf boxes,
+   [34] sky cells (atr_render_sky_cells): the wavefronts whose active lanes all fail every model's
+   first box test. */
 int atr_render_wave_trace(atr_ctx* ctx, const atr_camera* cam, const atr_tile* tiles, int32_t ntiles,
                           uint64_t seed, int32_t variant, uint64_t* out, int64_t cap, int64_t* nblocks);
 #ifdef __cplusplus
