@@ -3060,6 +3060,103 @@ int atr_denoise(atr_ctx* c, const float* color, const atr_denoise_guides* guides
     return ATR_OK;
 } ATR_ABI_CATCH
 
+void atr_default_accumulate_params(atr_accumulate_params* out) {
+    if (!out) return;
+    std::memset(out, 0, sizeof(*out));
+    out->alpha = 0.0f;           // the plain running mean up to max_length frames
+    out->alpha_moments = 0.0f;
+    out->max_length = 64;
+    out->plane_tolerance = 0.02f;
+    out->min_normal_dot = 0.9f;
+}
+
+// atr_accumulate's argument rules (atray.h), host only: the structs are read, no DEVICE pointer is followed.
+int atr_accumulate_check(const float* color, const atr_denoise_guides* guides, const atr_camera* prev_cam,
+                         const atr_denoise_guides* prev_guides, const atr_history* prev, int32_t width, int32_t height,
+                         const atr_accumulate_params* params, const atr_history* out, const float* variance) try {
+    if (!color || !params || !out || !out->color || !out->length) return ATR_E_INVALID;
+    if (width < 1 || width > kDenoiseMaxSide || height < 1 || height > kDenoiseMaxSide) return ATR_E_INVALID;
+    const atr_accumulate_params& ap = *params;
+    if (!(ap.alpha >= 0.0f && ap.alpha <= 1.0f) || !(ap.alpha_moments >= 0.0f && ap.alpha_moments <= 1.0f))
+        return ATR_E_INVALID;
+    if (ap.max_length < 1 || ap.max_length > kAccumulateMaxLength) return ATR_E_INVALID;
+    if (!std::isfinite(ap.plane_tolerance) || !(ap.plane_tolerance > 0.0f)) return ATR_E_INVALID;
+    if (!(ap.min_normal_dot >= -1.0f && ap.min_normal_dot <= 1.0f)) return ATR_E_INVALID;
+    for (int32_t r : ap.reserved)
+        if (r) return ATR_E_INVALID;
+    if (variance && !out->moments) return ATR_E_INVALID;
+    if (prev) {
+        if (!prev_cam || !prev_guides || !guides || !prev->color || !prev->length) return ATR_E_INVALID;
+        if (!guides->position || !prev_guides->position) return ATR_E_INVALID;
+        if (!guides->normal != !prev_guides->normal || !guides->ident != !prev_guides->ident) return ATR_E_INVALID;
+        if (!out->moments != !prev->moments) return ATR_E_INVALID;
+        if (out->color == prev->color || out->length == prev->length || (out->moments && out->moments == prev->moments))
+            return ATR_E_INVALID;
+        if (prev_cam->width != width || prev_cam->height != height) return ATR_E_INVALID;
+        const float k = prev_cam->h_fov * prev_cam->aspect_ratio;
+        if (!(std::isfinite(k) && k > 0.0f)) return ATR_E_INVALID;
+    }
+    return ATR_OK;
+} ATR_ABI_CATCH
+
+int atr_accumulate(atr_ctx* c, const float* color, const atr_denoise_guides* guides, const atr_camera* prev_cam,
+                   const atr_denoise_guides* prev_guides, const atr_history* prev, int32_t width, int32_t height,
+                   const atr_accumulate_params* params, const atr_history* out, float* variance, uint32_t* framebuffer,
+                   void* stream) try {
+    if (!c) return ATR_E_INVALID;
+    const int rc = atr_accumulate_check(color, guides, prev_cam, prev_guides, prev, width, height, params, out, variance);
+    if (rc) return rc;
+    const atr_denoise_guides none = {nullptr, nullptr, nullptr};
+    const atr_denoise_guides& g = guides ? *guides : none;
+    AccumulateParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.width = width;
+    P.height = height;
+    P.max_length = uint32_t(params->max_length);
+    P.alpha = params->alpha;
+    P.alpha_moments = params->alpha_moments;
+    P.plane_tolerance = params->plane_tolerance;
+    P.min_normal_dot = params->min_normal_dot;
+    P.hw = 0.5f * float(width);
+    P.hh = 0.5f * float(height);
+    P.fw = float(width);
+    P.fh = float(height);
+    P.color = color;
+    P.normal = g.normal;
+    P.position = g.position;
+    P.ident = g.ident;
+    if (prev) {
+        const atr_camera& pc = *prev_cam;
+        P.has_prev = 1;
+        P.k = pc.h_fov * pc.aspect_ratio;
+        const atr_vec3* src[4] = {&pc.eye, &pc.camera_x, &pc.camera_y, &pc.camera_z};
+        float* dst[4] = {P.eye, P.cx, P.cy, P.cz};
+        for (int i = 0; i < 4; ++i) dst[i][0] = src[i]->x, dst[i][1] = src[i]->y, dst[i][2] = src[i]->z;
+        P.prev_normal = prev_guides->normal;
+        P.prev_position = prev_guides->position;
+        P.prev_ident = prev_guides->ident;
+        P.prev_color = prev->color;
+        P.prev_moments = prev->moments;
+        P.prev_length = prev->length;
+    }
+    P.out_color = out->color;
+    P.out_moments = out->moments;
+    P.out_length = out->length;
+    P.variance = variance;
+    P.framebuffer = framebuffer;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = the null stream (HIP convention)
+    c->prog_active = false;
+    HIPCHK(hipEventRecord(c->ev_start, s));
+    HIPCHK(atr_launch_accumulate(P, s));
+    HIPCHK(record_stop(c, s, nullptr));
+    HIPCHK(note_launch(c, s));
+    c->have_render = true;
+    c->last_stream = s;
+    c->last_ntiles = 0;
+    return ATR_OK;
+} ATR_ABI_CATCH
+
 int atr_render_wait(atr_ctx* c, uint32_t timeout_ms, int32_t* tiles_done) try {
     if (!c) return ATR_E_INVALID;
     if (tiles_done) *tiles_done = 0;

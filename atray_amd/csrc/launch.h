@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "accumulate.h"
 #include "denoise.h"
 #include "engine.h"
 #include "texels.h"
@@ -58,6 +59,8 @@ hipError_t atr_launch_texel_fill(const atr::TexelImageParams& P, hipStream_t s);
 // denoise.hip
 hipError_t atr_launch_denoise_pack(const atr::DenoisePack& P, hipStream_t s);
 hipError_t atr_launch_denoise_pass(const atr::DenoisePass& P, int normal, int position, int colour, hipStream_t s);
+// accumulate.hip
+hipError_t atr_launch_accumulate(const atr::AccumulateParams& P, hipStream_t s);
 // plan.hip
 hipError_t atr_launch_plan(const atr::DBlock* base, int32_t nb, unsigned long long* cost,
                            unsigned long long* cost_last, void* work, atr::DBlock* out, int32_t max_split,

@@ -133,6 +133,15 @@ class atr_denoise_guides(C.Structure):
     _fields_ = [("normal", C.c_void_p), ("position", C.c_void_p), ("ident", C.c_void_p)]
 
 
+class atr_history(C.Structure):
+    _fields_ = [("color", C.c_void_p), ("moments", C.c_void_p), ("length", C.c_void_p)]
+
+
+class atr_accumulate_params(C.Structure):
+    _fields_ = [("alpha", C.c_float), ("alpha_moments", C.c_float), ("max_length", C.c_int32),
+                ("plane_tolerance", C.c_float), ("min_normal_dot", C.c_float), ("reserved", C.c_int32 * 3)]
+
+
 class atr_tuning(C.Structure):
     _fields_ = [("xcd_chunk", C.c_int32), ("frame_rotate", C.c_int32), ("hybrid_a", C.c_int32),
                 ("hybrid_b", C.c_int32), ("path_batch_log2", C.c_int32), ("cluster_size", C.c_int32),
@@ -164,6 +173,7 @@ EXPORTS = [
     "atr_render_fold_counters", "atr_camera_pads_row", "atr_default_denoise_params", "atr_denoise",
     "atr_render_leaf_box_counters", "atr_camera_leaf_boxes_row",
     "atr_render_sky_cells", "atr_scene_sky_record", "atr_sky_record_host",
+    "atr_default_accumulate_params", "atr_accumulate_check", "atr_accumulate",
 ]
 # the diagnostic build's extra symbols (include/atray_diag.h; make -C atray_amd/csrc DIAG=1)
 DIAG_EXPORTS = ["atr_render_wave_trace", "atr_render_phase_clocks", "atr_render_path_counters",
@@ -230,6 +240,11 @@ def lib():
         "atr_texels_to_image": ([vp, vp, vp, i64, i32, i32, i32, C.c_float * 3, vp, vp], C.c_int),
         "atr_default_denoise_params": ([P(atr_denoise_params)], None),
         "atr_denoise": ([vp, vp, P(atr_denoise_guides), i32, i32, P(atr_denoise_params), vp, vp, vp], C.c_int),
+        "atr_default_accumulate_params": ([P(atr_accumulate_params)], None),
+        "atr_accumulate_check": ([vp, P(atr_denoise_guides), P(atr_camera), P(atr_denoise_guides), P(atr_history), i32,
+                                  i32, P(atr_accumulate_params), P(atr_history), vp], C.c_int),
+        "atr_accumulate": ([vp, vp, P(atr_denoise_guides), P(atr_camera), P(atr_denoise_guides), P(atr_history), i32,
+                            i32, P(atr_accumulate_params), P(atr_history), vp, vp, vp], C.c_int),
         "atr_render_packed_size": ([vp, i32], i64),
         "atr_render_counters": ([vp, P(atr_camera), vp, i32, C.c_uint64, i32, i64 * 10], C.c_int),
         "atr_render_cull_counters": ([vp, P(atr_camera), vp, i32, C.c_uint64, i32, i64 * 5], C.c_int),
@@ -1066,6 +1081,94 @@ class Engine:
         return (nrm.reshape(h, w, 3).contiguous(), pos.reshape(h, w, 3).contiguous(),
                 ident.to(torch.int32).reshape(h, w).contiguous())
 
+    def accumulate(self, color, guides, prev=None, cam=None, alpha=0.0, alpha_moments=0.0, max_length=64,
+                   plane_tolerance=0.02, min_normal_dot=0.9, moments=True, out=None, variance=False, framebuffer=False,
+                   stream=None):
+        """atr_accumulate: this frame blended into the history reprojected from the previous camera
+        (atray.h has the formulas). color: a contiguous (H, W, 3) float32 tensor on the engine's device.
+        guides: (normal, position, ident) as render_guides returns them, (H, W, 3), (H, W, 3) float32 and
+        (H, W) int32 or uint32, any of them None (position is required once there is a history). prev:
+        None to start a history, else the dict an earlier call returned: "cam" (the atr_camera of that
+        frame), "guides" (its triple), "color", "moments" (or None), "length". cam: this frame's camera,
+        only stored in the returned dict for the next call. moments: whether a history that starts
+        carries moments (with prev, its own decides). out: None for new tensors, or a dict with "color"
+        (it may be `color` itself), "moments" and "length" to write, none of them prev's. Enqueued on
+        `stream` (a raw HIP stream), or torch's current one. Returns the new dict; with variance=True
+        and/or framebuffer=True a tuple (dict, variance (H, W) float32, framebuffer (H, W) int32) of the
+        requested ones; valid once the stream has run, e.g. after wait()."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if (not isinstance(color, torch.Tensor) or color.dtype != torch.float32 or color.dim() != 3
+                or color.shape[2] != 3 or color.device != dev or not color.is_contiguous()):
+            raise ValueError(f"color: a contiguous (H, W, 3) float32 tensor on {dev} is required")
+        h, w = int(color.shape[0]), int(color.shape[1])
+        kinds = (torch.int32,) + ((torch.uint32,) if hasattr(torch, "uint32") else ())
+
+        def image(name, a, dtypes, shape):
+            if a is None:
+                return
+            if (not isinstance(a, torch.Tensor) or a.dtype not in dtypes or tuple(a.shape) != shape
+                    or a.device != dev or not a.is_contiguous()):
+                what = " or ".join(str(d).replace("torch.", "") for d in dtypes)
+                raise ValueError(f"{name}: a contiguous {shape} {what} tensor on {dev} is required")
+
+        def triple(name, g):
+            if g is None:
+                g = (None, None, None)
+            if not isinstance(g, (tuple, list)) or len(g) != 3:
+                raise ValueError(f"{name}: (normal, position, ident) is required")
+            image(f"{name} normal", g[0], (torch.float32,), (h, w, 3))
+            image(f"{name} position", g[1], (torch.float32,), (h, w, 3))
+            image(f"{name} ident", g[2], kinds, (h, w))
+            return tuple(g)
+
+        guides = triple("guides", guides)
+        if prev is not None:
+            missing = [k for k in ("cam", "guides", "color", "length") if prev.get(k) is None]
+            if missing:
+                raise ValueError(f"prev: entries {missing} are required")
+            pg = triple("prev guides", prev["guides"])
+            image("prev color", prev["color"], (torch.float32,), (h, w, 3))
+            image("prev moments", prev.get("moments"), (torch.float32,), (h, w, 2))
+            image("prev length", prev["length"], kinds, (h, w))
+            moments = prev.get("moments") is not None
+        new = dict(out) if out is not None else {}
+        image("out color", new.get("color"), (torch.float32,), (h, w, 3))
+        image("out moments", new.get("moments"), (torch.float32,), (h, w, 2))
+        image("out length", new.get("length"), kinds, (h, w))
+        if new.get("color") is None:
+            new["color"] = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
+        if new.get("length") is None:
+            new["length"] = torch.empty((h, w), dtype=torch.int32, device=dev)
+        if not moments:
+            new["moments"] = None
+        elif new.get("moments") is None:
+            new["moments"] = torch.empty((h, w, 2), dtype=torch.float32, device=dev)
+        if variance and not moments:
+            raise ValueError("variance needs a history with moments")
+        var = torch.empty((h, w), dtype=torch.float32, device=dev) if variance else None
+        fb = torch.empty((h, w), dtype=torch.int32, device=dev) if framebuffer else None
+        addr = lambda a: a.data_ptr() if a is not None and a.numel() else None  # noqa: E731
+        ptr = lambda a: C.c_void_p(addr(a)) if addr(a) else None  # noqa: E731
+        g = atr_denoise_guides(*[addr(a) for a in guides])
+        ho = atr_history(addr(new["color"]), addr(new["moments"]), addr(new["length"]))
+        params = atr_accumulate_params(float(alpha), float(alpha_moments), int(max_length), float(plane_tolerance),
+                                       float(min_normal_dot))
+        if prev is not None:
+            pgs = atr_denoise_guides(*[addr(a) for a in pg])
+            hp = atr_history(addr(prev["color"]), addr(prev.get("moments")), addr(prev["length"]))
+            pargs = (C.byref(prev["cam"]), C.byref(pgs), C.byref(hp))
+        else:
+            pargs = (None, None, None)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        check(lib().atr_accumulate(self.h, ptr(color), C.byref(g), *pargs, w, h, C.byref(params), C.byref(ho),
+                                   ptr(var), ptr(fb), C.c_void_p(stream) if stream else None), "accumulate")
+        new["cam"] = atr_camera.from_buffer_copy(cam) if cam is not None else None
+        new["guides"] = guides
+        extra = tuple(a for a, on in ((var, variance), (fb, framebuffer)) if on)
+        return (new,) + extra if extra else new
+
     def bake_lightmap(self, mesh, width, height, nsamples, bounces=None, t_max=None, seed=0, passes=2, flip=False,
                       denoise=None):
         """A lightmap of `mesh` in three device calls: mesh_texels, a hemisphere gather on the texels'
@@ -1403,6 +1506,47 @@ class Engine:
             self.close()
         except Exception:
             pass
+
+
+class TemporalAccumulator:
+    """Frames of a static scene accumulated across cameras with Engine.accumulate: two history sets,
+    ping-ponged, and the previous frame's camera and guides. A change of frame size starts the history
+    again, as reset() does. Keywords are accumulate()'s parameters (alpha, alpha_moments, max_length,
+    plane_tolerance, min_normal_dot)."""
+
+    def __init__(self, engine, **params):
+        bad = [k for k in params
+               if k not in ("alpha", "alpha_moments", "max_length", "plane_tolerance", "min_normal_dot")]
+        if bad:
+            raise ValueError(f"unknown parameters {bad}")
+        self.engine, self.params = engine, params
+        self.sets, self.prev, self.index = [None, None], None, 0
+
+    def reset(self):
+        """The next push starts a new history."""
+        self.prev = None
+
+    def push(self, cam, color, guides=None, stream=None):
+        """One frame: `color` (H, W, 3) float32 as rendered from `cam`, guides (normal, position, ident)
+        or None for render_guides(cam). Returns (accumulated (H, W, 3), variance (H, W)); the accumulated
+        tensor belongs to the history and is overwritten by the push after the next. On torch's current
+        stream, or `stream` if the guides are supplied."""
+        import torch
+        if guides is None:
+            guides = self.engine.render_guides(cam, stream=stream)
+        h, w = int(color.shape[0]), int(color.shape[1])
+        if self.prev is not None and tuple(self.prev["color"].shape[:2]) != (h, w):
+            self.prev = None
+        k = self.index
+        if self.sets[k] is None or tuple(self.sets[k]["color"].shape[:2]) != (h, w):
+            dev = color.device
+            self.sets[k] = {"color": torch.empty((h, w, 3), dtype=torch.float32, device=dev),
+                            "moments": torch.empty((h, w, 2), dtype=torch.float32, device=dev),
+                            "length": torch.empty((h, w), dtype=torch.int32, device=dev)}
+        new, var = self.engine.accumulate(color, guides, prev=self.prev, cam=cam, out=self.sets[k], variance=True,
+                                          stream=stream, **self.params)
+        self.prev, self.index = new, k ^ 1
+        return new["color"], var
 
 
 def pack_bgr_masked_bound(npixels):

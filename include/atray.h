@@ -30,7 +30,8 @@ extern "C" {
    atr_gather_directions likewise; atr_radiance_rays and atr_radiance_out likewise;
    atr_gather_radiance and atr_gather_radiance_out likewise; atr_mesh_texels, atr_texels_out and
    atr_texels_to_image likewise; atr_denoise, atr_denoise_params, atr_denoise_guides and
-   atr_default_denoise_params likewise. */
+   atr_default_denoise_params likewise; atr_accumulate, atr_accumulate_check, atr_history,
+   atr_accumulate_params and atr_default_accumulate_params likewise. */
 #define ATR_ABI_VERSION 2
 
 enum {
@@ -931,6 +932,90 @@ void atr_default_denoise_params(atr_denoise_params* out);   /* 5, 0.01f, 0.0f, 5
 int atr_denoise(atr_ctx* ctx, const float* color, const atr_denoise_guides* guides, int32_t width,
                 int32_t height, const atr_denoise_params* params, float* out, uint32_t* framebuffer,
                 void* stream);
+
+/* Temporal accumulation of a frame into a history that is reprojected from the previous camera: a
+   static scene and a world-space position per pixel need no motion vectors, the previous camera alone
+   says where a surface point was on the previous film. The caller keeps two atr_history sets and
+   ping-pongs them, and keeps the previous frame's guides (atr_denoise_guides, as atr_denoise takes
+   them; Engine.render_guides makes them). Every f32 operation below is separately rounded, in the
+   order written (tests/c/accumulate_ref.c restates them in plain C); dot and len2 are atr_denoise's.
+   Buffers. All DEVICE, IMAGE layout. color: 3 f32 per pixel, this frame. guides: this frame's;
+   prev_cam, prev_guides, prev: the previous frame's camera, guides and history (the `out` of the call
+   before). prev == NULL starts a history: prev_cam and prev_guides are ignored and every live pixel
+   takes the "no history" branch; guides may then be NULL (three NULL pointers). out: the new history.
+   variance (optional): one f32 per pixel. framebuffer (optional): BGRX u32 per pixel, made from
+   out.color by atr_denoise's clamp and quantisation, for every pixel.
+   Inert pixels: atr_denoise's rule on this frame's inputs (ident given and ATR_DENOISE_EMPTY; a colour
+   float that is not finite; normal given and one of its floats not finite; position given and one of
+   its floats not finite). An inert pixel's out.color is the input colour's bits, its out.moments 0, 0,
+   its out.length 0, its variance 0.
+   Host constants: k = prev_cam->h_fov * prev_cam->aspect_ratio; hw = 0.5f * float(width), hh = 0.5f *
+   float(height).
+   Reprojection of a live pixel P (position p, normal n, colour c) inverts the kernels' film mapping
+   film = frame_center + camera_x*fx + camera_y*fy, the film at distance 1 along -camera_z, fx = ((-1 +
+   2*(x/W))*h_fov)*aspect, fy = -1 + 2*(y/H); eye and the axes are prev_cam's:
+     v = p - eye; depth = -dot(v, camera_z); no history unless depth > 0;
+     a = dot(v, camera_x) / depth; b = dot(v, camera_y) / depth;
+     sx = (a / k + 1.0f) * hw; sy = (b + 1.0f) * hh;
+     no history unless sx >= -1.0f && sx < float(width) && sy >= -1.0f && sy < float(height)
+     (every comparison is written so that a NaN fails it);
+     fx0 = floorf(sx), x0 = int(fx0), tx = sx - fx0; fy0 = floorf(sy), y0 = int(fy0), ty = sy - fy0.
+   Taps: four, in the order (dy, dx) = (0,0), (0,1), (1,0), (1,1); Q = (x0+dx, y0+dy) in the previous
+   frame, w = (dx ? tx : 1.0f - tx) * (dy ? ty : 1.0f - ty). Q is skipped if
+     1. it lies outside the image;
+     2. prev.length[Q] == 0;
+     3. idents are given and prev_ident_Q != ident_P, or prev_ident_Q == ATR_DENOISE_EMPTY;
+     4. normals are given and !(dot(n, n_Q) >= min_normal_dot);
+     5. with dv = p_Q - p, e2 = e*e where e = dot(n, dv) when normals are given, else e2 = len2(dv), and
+        tol = plane_tolerance * depth: !(e2 <= tol*tol);
+     6. one of Q's three history colour floats is not finite or, moments given, one of its two moments;
+     7. !(w > 0).
+   A kept tap adds: per channel sum = sum + hc_Q * w; the two moments msum = msum + m_Q * w; wsum =
+   wsum + w; nmin = min(nmin, length_Q).
+   Blend. l = (0.2126f*c.x + 0.7152f*c.y) + 0.0722f*c.z. If wsum > 0: h = sum / wsum (three divisions),
+   hm = msum / wsum, len = min(nmin, max_length - 1) + 1, aw = 1.0f / float(len), ac = alpha > aw ?
+   alpha : aw, am = alpha_moments > aw ? alpha_moments : aw; out.color = h + (c - h) * ac; m1 = hm.x +
+   (l - hm.x) * am; m2 = hm.y + (l*l - hm.y) * am; out.length = len. Else out.color = c (its bits), m1 =
+   l, m2 = l*l, out.length = 1. out.moments = m1, m2; variance = m2 - m1*m1, then variance > 0 ?
+   variance : 0.
+   Pointers. color, out->color and out->length are required. With prev: prev_cam, prev_guides,
+   guides->position, prev_guides->position, prev->color and prev->length are required; normal is in
+   both guides or in neither, ident likewise, moments in both histories or in neither. variance needs
+   out->moments. out->color == color is allowed (a lane reads only its own pixel of color). No out
+   pointer may equal the corresponding prev pointer; only pointer equality is checked, other overlap
+   is the caller's error.
+   Asynchronous on `stream`; atr_render_wait covers it (tiles_done 0), atr_last_kernel_ms times it. No
+   scene and no workspace are needed.
+   ATR_E_INVALID, with nothing enqueued or written: a NULL among the required arguments (ctx, params,
+   out included); width or height outside 1..16,384; with prev, prev_cam->width/height other than
+   width/height, or a k that is not finite and > 0; alpha or alpha_moments outside [0, 1] or NaN;
+   max_length outside 1..2^24; plane_tolerance not finite or not > 0; min_normal_dot outside [-1, 1] or
+   NaN; non-zero reserved; any pointer rule above. atr_accumulate_check is that validation alone, on
+   the host, with no context and no device (no pointer into DEVICE memory is followed): ATR_OK or
+   ATR_E_INVALID. No struct and no ABI version change. */
+typedef struct {            /* DEVICE, IMAGE layout, caller-owned; one frame's history */
+    float*    color;        /* 3 per pixel: the accumulated colour */
+    float*    moments;      /* 2 per pixel: accumulated luminance and luminance^2; may be NULL */
+    uint32_t* length;       /* per pixel: frames accumulated (0 = inert pixel, 1 = no history found) */
+} atr_history;
+typedef struct {
+    float   alpha;           /* 0..1: lower bound of the new frame's weight for colour */
+    float   alpha_moments;   /* 0..1: the same for the moments */
+    int32_t max_length;      /* 1..2^24: the history length saturates here */
+    float   plane_tolerance; /* > 0, finite: a tap's distance from P's tangent plane, per unit of depth */
+    float   min_normal_dot;  /* -1..1: a tap's normal must reach this dot with P's; ignored without normals */
+    int32_t reserved[3];     /* must be 0 */
+} atr_accumulate_params;
+void atr_default_accumulate_params(atr_accumulate_params* out);   /* 0, 0, 64, 0.02f, 0.9f, zeros */
+int atr_accumulate_check(const float* color, const atr_denoise_guides* guides, const atr_camera* prev_cam,
+                         const atr_denoise_guides* prev_guides, const atr_history* prev, int32_t width,
+                         int32_t height, const atr_accumulate_params* params, const atr_history* out,
+                         const float* variance);
+int atr_accumulate(atr_ctx* ctx, const float* color, const atr_denoise_guides* guides,
+                   const atr_camera* prev_cam, const atr_denoise_guides* prev_guides,
+                   const atr_history* prev, int32_t width, int32_t height,
+                   const atr_accumulate_params* params, const atr_history* out,
+                   float* variance, uint32_t* framebuffer, void* stream);
 
 /* wait_for_render_from_camera_to_finish: 1 = still running after timeout_ms, 0 = done,
    <0 = error. tiles_done (optional) = tiles of the last render known complete (progress). */
