@@ -336,6 +336,16 @@ struct atr_ctx {
         hipStream_t stream = nullptr;
         bool used = false;
     } dn_ws;
+    // Variance-guided denoise workspace (atr_denoise_variance, denoise_variance.hip), grow-only and apart
+    // from dn_ws, so that an atr_denoise and an atr_denoise_variance on two streams share nothing:
+    // `color` = the two ping-pong images of 16-B colour records, `var` = the two images of 8-B
+    // {variance, luminance} records, `guides` as in dn_ws; ordered between streams by `ev` as dn_ws is.
+    struct DenoiseVarWS {
+        DevBuf color, var, guides;
+        hipEvent_t ev = nullptr;
+        hipStream_t stream = nullptr;
+        bool used = false;
+    } dnv_ws;
 };
 
 namespace {
@@ -1485,6 +1495,9 @@ int atr_destroy(atr_ctx* c) try {
     for (DevBuf* d : {&c->dn_ws.color, &c->dn_ws.guides})
         if (d->p) (void)hipFree(d->p);
     if (c->dn_ws.ev) (void)hipEventDestroy(c->dn_ws.ev);
+    for (DevBuf* d : {&c->dnv_ws.color, &c->dnv_ws.var, &c->dnv_ws.guides})
+        if (d->p) (void)hipFree(d->p);
+    if (c->dnv_ws.ev) (void)hipEventDestroy(c->dnv_ws.ev);
     for (atr_ctx::PadSlot& q : c->pad_slot) {
         if (q.mem.p) (void)hipFree(q.mem.p);
         if (q.built) (void)hipEventDestroy(q.built);
@@ -3050,6 +3063,146 @@ int atr_denoise(atr_ctx* c, const float* color, const atr_denoise_guides* guides
         P.out = last ? out : nullptr;
         P.framebuffer = last ? framebuffer : nullptr;
         HIPCHK(atr_launch_denoise_pass(P, g.normal != nullptr, position_on, colour_on, s));
+    }
+    HIPCHK(hipEventRecord(ws.ev, s));
+    HIPCHK(record_stop(c, s, nullptr));
+    HIPCHK(note_launch(c, s));
+    c->have_render = true;
+    c->last_stream = s;
+    c->last_ntiles = 0;
+    return ATR_OK;
+} ATR_ABI_CATCH
+
+void atr_default_denoise_variance_params(atr_denoise_variance_params* out) {
+    if (!out) return;
+    std::memset(out, 0, sizeof(*out));
+    out->passes = 3;  // the grid point with the lowest worst-seed error under its conditions
+    out->sigma_luminance = 8.0f;
+    out->luminance_floor = 1e-4f;
+    out->sigma_position = 0.0f;
+    out->normal_power_log2 = 5;
+    out->spatial_below = 4;
+}
+
+// atr_denoise_variance's argument rules (atray.h), host only: the structs are read, no DEVICE pointer is followed.
+int atr_denoise_variance_check(const float* color, const float* variance, const atr_denoise_guides* guides,
+                               const float* moments, const uint32_t* length, int32_t width, int32_t height,
+                               const atr_denoise_variance_params* params, const float* out, const float* variance_out,
+                               const uint32_t* framebuffer) try {
+    (void)variance_out;  // optional, and it may be `variance` itself
+    if (!params || !color || !variance || (!out && !framebuffer)) return ATR_E_INVALID;
+    if (!moments != !length) return ATR_E_INVALID;
+    if (width < 1 || width > kDenoiseMaxSide || height < 1 || height > kDenoiseMaxSide) return ATR_E_INVALID;
+    const atr_denoise_variance_params& dp = *params;
+    if (dp.passes < 1 || dp.passes > kDenoiseMaxPasses || dp.normal_power_log2 < 0 ||
+        dp.normal_power_log2 > kDenoiseMaxNormalPower || dp.spatial_below < 0 ||
+        dp.spatial_below > kDenoiseVarMaxSpatialBelow)
+        return ATR_E_INVALID;
+    if (!(dp.sigma_luminance >= 0.0f) || !std::isfinite(dp.sigma_luminance) || !(dp.luminance_floor > 0.0f) ||
+        !std::isfinite(dp.luminance_floor) || !(dp.sigma_position >= 0.0f) || !std::isfinite(dp.sigma_position))
+        return ATR_E_INVALID;
+    for (int32_t r : dp.reserved)
+        if (r) return ATR_E_INVALID;
+    if (guides && guides->position && dp.sigma_position > 0.0f)  // the position term is on
+        for (int p = 0; p < dp.passes; ++p) {
+            const float sp = dp.sigma_position * float(1 << p);
+            const float kp = 1.0f / (sp * sp);
+            if (!(std::isfinite(kp) && kp > 0.0f)) return ATR_E_INVALID;
+        }
+    return ATR_OK;
+} ATR_ABI_CATCH
+
+int atr_denoise_variance(atr_ctx* c, const float* color, const float* variance, const atr_denoise_guides* guides,
+                         const float* moments, const uint32_t* length, int32_t width, int32_t height,
+                         const atr_denoise_variance_params* params, float* out, float* variance_out,
+                         uint32_t* framebuffer, void* stream) try {
+    if (!c) return ATR_E_INVALID;
+    const int vrc = atr_denoise_variance_check(color, variance, guides, moments, length, width, height, params, out,
+                                               variance_out, framebuffer);
+    if (vrc) return vrc;
+    const atr_denoise_variance_params& dp = *params;
+    const atr_denoise_guides none = {nullptr, nullptr, nullptr};
+    const atr_denoise_guides& g = guides ? *guides : none;
+    const bool luminance_on = dp.sigma_luminance > 0.0f, position_on = g.position && dp.sigma_position > 0.0f;
+    const bool estimate_on = moments && dp.spatial_below > 0;
+    float kp[kDenoiseMaxPasses];
+    for (int p = 0; p < dp.passes; ++p) {
+        const float sp = dp.sigma_position * float(1 << p);
+        kp[p] = position_on ? 1.0f / (sp * sp) : 0.0f;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = the null stream (HIP convention)
+    atr_ctx::DenoiseVarWS& ws = c->dnv_ws;
+    if (!ws.ev) HIPCHK(hipEventCreateWithFlags(&ws.ev, hipEventDisableTiming));
+    const size_t npix = size_t(width) * size_t(height), image = npix * sizeof(float4_t), vimage = npix * sizeof(float2_t);
+    const size_t need_guides = image * ((g.normal ? 1 : 0) + (g.position ? 1 : 0));
+    if (!ws.color.p || ws.color.n < 2 * image || !ws.var.p || ws.var.n < 2 * vimage ||
+        ws.guides.n < need_guides) {  // grow: after the last call that used it
+        if (ws.used) HIPCHK(hipEventSynchronize(ws.ev));
+        int rc;
+        if ((rc = ensure_buf(ws.color, 2 * image, false))) return rc;
+        if ((rc = ensure_buf(ws.var, 2 * vimage, false))) return rc;
+        if (need_guides && (rc = ensure_buf(ws.guides, need_guides, false))) return rc;
+    }
+    if (ws.used && ws.stream != s) HIPCHK(hipStreamWaitEvent(s, ws.ev, 0));
+    c->prog_active = false;
+    HIPCHK(hipEventRecord(c->ev_start, s));
+    ws.used = true;  // from here on kernels of this call may be in flight on s
+    ws.stream = s;
+    float4_t* img[2] = {static_cast<float4_t*>(ws.color.p), static_cast<float4_t*>(ws.color.p) + npix};
+    float2_t* vl[2] = {static_cast<float2_t*>(ws.var.p), static_cast<float2_t*>(ws.var.p) + npix};
+    float4_t* rec = static_cast<float4_t*>(ws.guides.p);
+    DenoiseVarPack K;
+    std::memset(&K, 0, sizeof(K));
+    K.color = color;
+    K.variance = variance;
+    K.normal = g.normal;
+    K.position = g.position;
+    K.ident = g.ident;
+    K.npixels = int64_t(npix);
+    K.color4 = img[0];
+    K.vl = vl[0];
+    K.normal4 = g.normal ? rec : nullptr;
+    K.position4 = g.position ? rec + (g.normal ? npix : 0) : nullptr;
+    HIPCHK(atr_launch_denoise_variance_pack(K, s));
+    if (estimate_on) {
+        DenoiseVarEstimate Q;
+        std::memset(&Q, 0, sizeof(Q));
+        Q.width = width;
+        Q.height = height;
+        Q.normal_power = dp.normal_power_log2;
+        Q.below = uint32_t(dp.spatial_below);
+        Q.kp = kp[0];
+        Q.fbelow = float(dp.spatial_below);
+        Q.color4 = img[0];
+        Q.normal4 = K.normal4;
+        Q.position4 = K.position4;
+        Q.moments = reinterpret_cast<const float2_t*>(moments);
+        Q.length = length;
+        Q.vl = vl[0];
+        HIPCHK(atr_launch_denoise_variance_estimate(Q, g.normal != nullptr, position_on, s));
+    }
+    DenoiseVarPass P;
+    std::memset(&P, 0, sizeof(P));
+    P.width = width;
+    P.height = height;
+    P.normal_power = dp.normal_power_log2;
+    P.sigma_luminance = dp.sigma_luminance;
+    P.luminance_floor = dp.luminance_floor;
+    P.normal4 = K.normal4;
+    P.position4 = K.position4;
+    for (int p = 0; p < dp.passes; ++p) {
+        const bool last = p == dp.passes - 1;
+        P.step = 1 << p;
+        P.kp = kp[p];
+        P.src = img[p & 1];
+        P.src_vl = vl[p & 1];
+        P.dst = last ? nullptr : img[(p & 1) ^ 1];
+        P.dst_vl = last ? nullptr : vl[(p & 1) ^ 1];
+        P.out = last ? out : nullptr;
+        P.variance_out = last ? variance_out : nullptr;
+        P.framebuffer = last ? framebuffer : nullptr;
+        HIPCHK(atr_launch_denoise_variance_pass(P, g.normal != nullptr, position_on, luminance_on, s));
     }
     HIPCHK(hipEventRecord(ws.ev, s));
     HIPCHK(record_stop(c, s, nullptr));

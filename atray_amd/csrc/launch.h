@@ -5,6 +5,7 @@
 
 #include "accumulate.h"
 #include "denoise.h"
+#include "denoise_variance.h"
 #include "engine.h"
 #include "texels.h"
 
@@ -59,6 +60,11 @@ hipError_t atr_launch_texel_fill(const atr::TexelImageParams& P, hipStream_t s);
 // denoise.hip
 hipError_t atr_launch_denoise_pack(const atr::DenoisePack& P, hipStream_t s);
 hipError_t atr_launch_denoise_pass(const atr::DenoisePass& P, int normal, int position, int colour, hipStream_t s);
+// denoise_variance.hip
+hipError_t atr_launch_denoise_variance_pack(const atr::DenoiseVarPack& P, hipStream_t s);
+hipError_t atr_launch_denoise_variance_estimate(const atr::DenoiseVarEstimate& P, int normal, int position, hipStream_t s);
+hipError_t atr_launch_denoise_variance_pass(const atr::DenoiseVarPass& P, int normal, int position, int luminance,
+                                            hipStream_t s);
 // accumulate.hip
 hipError_t atr_launch_accumulate(const atr::AccumulateParams& P, hipStream_t s);
 // plan.hip

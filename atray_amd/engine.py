@@ -142,6 +142,12 @@ class atr_accumulate_params(C.Structure):
                 ("plane_tolerance", C.c_float), ("min_normal_dot", C.c_float), ("reserved", C.c_int32 * 3)]
 
 
+class atr_denoise_variance_params(C.Structure):
+    _fields_ = [("passes", C.c_int32), ("sigma_luminance", C.c_float), ("luminance_floor", C.c_float),
+                ("sigma_position", C.c_float), ("normal_power_log2", C.c_int32), ("spatial_below", C.c_int32),
+                ("reserved", C.c_int32 * 2)]
+
+
 class atr_tuning(C.Structure):
     _fields_ = [("xcd_chunk", C.c_int32), ("frame_rotate", C.c_int32), ("hybrid_a", C.c_int32),
                 ("hybrid_b", C.c_int32), ("path_batch_log2", C.c_int32), ("cluster_size", C.c_int32),
@@ -174,6 +180,7 @@ EXPORTS = [
     "atr_render_leaf_box_counters", "atr_camera_leaf_boxes_row",
     "atr_render_sky_cells", "atr_scene_sky_record", "atr_sky_record_host",
     "atr_default_accumulate_params", "atr_accumulate_check", "atr_accumulate",
+    "atr_default_denoise_variance_params", "atr_denoise_variance_check", "atr_denoise_variance",
 ]
 # the diagnostic build's extra symbols (include/atray_diag.h; make -C atray_amd/csrc DIAG=1)
 DIAG_EXPORTS = ["atr_render_wave_trace", "atr_render_phase_clocks", "atr_render_path_counters",
@@ -245,6 +252,11 @@ def lib():
                                   i32, P(atr_accumulate_params), P(atr_history), vp], C.c_int),
         "atr_accumulate": ([vp, vp, P(atr_denoise_guides), P(atr_camera), P(atr_denoise_guides), P(atr_history), i32,
                             i32, P(atr_accumulate_params), P(atr_history), vp, vp, vp], C.c_int),
+        "atr_default_denoise_variance_params": ([P(atr_denoise_variance_params)], None),
+        "atr_denoise_variance_check": ([vp, vp, P(atr_denoise_guides), vp, vp, i32, i32,
+                                        P(atr_denoise_variance_params), vp, vp, vp], C.c_int),
+        "atr_denoise_variance": ([vp, vp, vp, P(atr_denoise_guides), vp, vp, i32, i32,
+                                  P(atr_denoise_variance_params), vp, vp, vp, vp], C.c_int),
         "atr_render_packed_size": ([vp, i32], i64),
         "atr_render_counters": ([vp, P(atr_camera), vp, i32, C.c_uint64, i32, i64 * 10], C.c_int),
         "atr_render_cull_counters": ([vp, P(atr_camera), vp, i32, C.c_uint64, i32, i64 * 5], C.c_int),
@@ -1063,6 +1075,63 @@ class Engine:
                                 C.c_void_p(stream) if stream else None), "denoise")
         return (out, fb) if framebuffer else out
 
+    def denoise_variance(self, color, variance, normal=None, position=None, ident=None, moments=None, length=None,
+                         passes=3, sigma_luminance=8.0, luminance_floor=1e-4, sigma_position=0.0, normal_power_log2=5,
+                         spatial_below=4, out=None, variance_out=False, framebuffer=False, stream=None):
+        """atr_denoise_variance: the variance-guided a-trous filter (atray.h has the formulas). color,
+        normal, position, ident and out as in denoise(); variance: a contiguous (H, W) float32 tensor, the
+        variance of each pixel's luminance (accumulate()'s); moments (H, W, 2) float32 and length (H, W)
+        int32 or uint32: a history's, both or neither, for the spatial estimate of pixels whose length
+        is below spatial_below. variance_out: False, True for a new (H, W) float32 tensor, or a tensor
+        to write (it may be `variance` itself). Enqueued on `stream` (a raw HIP stream), or torch's
+        current one. Returns the image, or a tuple (image, variance_out, framebuffer) of the requested
+        ones; valid once the stream has run, e.g. after wait()."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if (not isinstance(color, torch.Tensor) or color.dtype != torch.float32 or color.dim() != 3
+                or color.shape[2] != 3 or color.device != dev or not color.is_contiguous()):
+            raise ValueError(f"color: a contiguous (H, W, 3) float32 tensor on {dev} is required")
+        h, w = int(color.shape[0]), int(color.shape[1])
+        kinds = (torch.int32,) + ((torch.uint32,) if hasattr(torch, "uint32") else ())
+
+        def image(name, a, dtypes, shape):
+            if (not isinstance(a, torch.Tensor) or a.dtype not in dtypes or tuple(a.shape) != shape
+                    or a.device != dev or not a.is_contiguous()):
+                what = " or ".join(str(d).replace("torch.", "") for d in dtypes)
+                raise ValueError(f"{name}: a contiguous {shape} {what} tensor on {dev} is required")
+
+        image("variance", variance, (torch.float32,), (h, w))
+        for name, a in (("normal", normal), ("position", position), ("out", out)):
+            if a is not None:
+                image(name, a, (torch.float32,), (h, w, 3))
+        if ident is not None:
+            image("ident", ident, kinds, (h, w))
+        if (moments is None) != (length is None):
+            raise ValueError("moments and length: both or neither")
+        if moments is not None:
+            image("moments", moments, (torch.float32,), (h, w, 2))
+            image("length", length, kinds, (h, w))
+        if isinstance(variance_out, torch.Tensor):
+            image("variance_out", variance_out, (torch.float32,), (h, w))
+            vout = variance_out
+        else:
+            vout = torch.empty((h, w), dtype=torch.float32, device=dev) if variance_out else None
+        if out is None:
+            out = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
+        fb = torch.empty((h, w), dtype=torch.int32, device=dev) if framebuffer else None
+        ptr = lambda a: C.c_void_p(a.data_ptr()) if a is not None and a.numel() else None  # noqa: E731
+        guides = atr_denoise_guides(*[a.data_ptr() if a is not None and a.numel() else None
+                                      for a in (normal, position, ident)])
+        params = atr_denoise_variance_params(int(passes), float(sigma_luminance), float(luminance_floor),
+                                             float(sigma_position), int(normal_power_log2), int(spatial_below))
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        check(lib().atr_denoise_variance(self.h, ptr(color), ptr(variance), C.byref(guides), ptr(moments), ptr(length),
+                                         w, h, C.byref(params), ptr(out), ptr(vout), ptr(fb),
+                                         C.c_void_p(stream) if stream else None), "denoise_variance")
+        extra = tuple(a for a, on in ((vout, vout is not None), (fb, framebuffer)) if on)
+        return (out,) + extra if extra else out
+
     def render_guides(self, cam, stream=None):
         """The denoiser's guides for a frame of `cam`: trace_rays on camera_rays(cam), then (normal,
         position, ident) as (H, W, 3), (H, W, 3) float32 and (H, W) int32 tensors in the render's IMAGE
@@ -1520,11 +1589,11 @@ class TemporalAccumulator:
         if bad:
             raise ValueError(f"unknown parameters {bad}")
         self.engine, self.params = engine, params
-        self.sets, self.prev, self.index = [None, None], None, 0
+        self.sets, self.prev, self.index, self.variance = [None, None], None, 0, None
 
     def reset(self):
         """The next push starts a new history."""
-        self.prev = None
+        self.prev = self.variance = None
 
     def push(self, cam, color, guides=None, stream=None):
         """One frame: `color` (H, W, 3) float32 as rendered from `cam`, guides (normal, position, ident)
@@ -1545,8 +1614,24 @@ class TemporalAccumulator:
                             "length": torch.empty((h, w), dtype=torch.int32, device=dev)}
         new, var = self.engine.accumulate(color, guides, prev=self.prev, cam=cam, out=self.sets[k], variance=True,
                                           stream=stream, **self.params)
-        self.prev, self.index = new, k ^ 1
+        self.prev, self.index, self.variance = new, k ^ 1, var
         return new["color"], var
+
+    def filtered(self, stream=None, **params):
+        """The last push's accumulated frame through Engine.denoise_variance, with its variance, moments,
+        length and guides; keywords are denoise_variance()'s parameters and framebuffer. Returns a new
+        image (with framebuffer=True, (image, framebuffer)); the history is read, never written, so the
+        next push sees what it would have seen."""
+        bad = [k for k in params if k not in ("passes", "sigma_luminance", "luminance_floor", "sigma_position",
+                                              "normal_power_log2", "spatial_below", "framebuffer")]
+        if bad:
+            raise ValueError(f"unknown parameters {bad}")
+        if self.prev is None or self.variance is None:
+            raise ValueError("filtered() needs a push first")
+        normal, position, ident = self.prev["guides"]
+        return self.engine.denoise_variance(self.prev["color"], self.variance, normal, position, ident,
+                                            moments=self.prev["moments"], length=self.prev["length"], stream=stream,
+                                            **params)
 
 
 def pack_bgr_masked_bound(npixels):

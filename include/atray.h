@@ -31,7 +31,9 @@ extern "C" {
    atr_gather_radiance and atr_gather_radiance_out likewise; atr_mesh_texels, atr_texels_out and
    atr_texels_to_image likewise; atr_denoise, atr_denoise_params, atr_denoise_guides and
    atr_default_denoise_params likewise; atr_accumulate, atr_accumulate_check, atr_history,
-   atr_accumulate_params and atr_default_accumulate_params likewise. */
+   atr_accumulate_params and atr_default_accumulate_params likewise; atr_denoise_variance,
+   atr_denoise_variance_check, atr_denoise_variance_params and atr_default_denoise_variance_params
+   likewise. */
 #define ATR_ABI_VERSION 2
 
 enum {
@@ -1016,6 +1018,80 @@ int atr_accumulate(atr_ctx* ctx, const float* color, const atr_denoise_guides* g
                    const atr_history* prev, int32_t width, int32_t height,
                    const atr_accumulate_params* params, const atr_history* out,
                    float* variance, uint32_t* framebuffer, void* stream);
+
+/* Variance-guided denoising: the spatial stage of SVGF (Schied et al. 2017) on atr_denoise's a-trous
+   pattern, for frames whose noise differs from pixel to pixel, such as atr_accumulate's output (its
+   `variance`, and its history's moments and length, are this call's inputs). The luminance stopping
+   weight is scaled per pixel by the local standard deviation, the variance is filtered along with the
+   colour, and a pixel whose history is too short to have a variance takes one from its neighbours'
+   moments. Every f32 operation below is separately rounded, in the order written
+   (tests/c/denoise_variance_ref.c restates them in plain C); divisions and sqrtf are IEEE; dot and len2
+   are atr_denoise's; lum(c) = (0.2126f*c.x + 0.7152f*c.y) + 0.0722f*c.z is atr_accumulate's.
+   Buffers. All DEVICE, IMAGE layout. color: 3 f32 per pixel; variance: 1 f32 per pixel, the variance of
+   the pixel's luminance; both required. guides: atr_denoise's, each optional, NULL = three NULLs.
+   moments (2 f32 per pixel) and length (u32 per pixel): an atr_history's, both given or both NULL. out
+   (3 f32 per pixel), variance_out (1 f32 per pixel) and framebuffer (BGRX u32 per pixel, atr_denoise's
+   clamp and quantisation of the result) are each optional; at least one of out and framebuffer is
+   non-NULL. out == color and variance_out == variance are allowed: every input is read in full before
+   any output is written; any other overlap is the caller's error and is not checked.
+   Inert pixels: atr_denoise's rule (ident given and ATR_DENOISE_EMPTY; a colour, normal or position
+   float that is not finite); the variance makes no pixel inert. An inert pixel keeps its colour bits,
+   has variance_out 0 and is never a tap.
+   Variance at the start, per live pixel: v = (variance > 0 && variance < inf) ? variance : 0 (a NaN, a
+   negative value and an infinity give 0).
+   Spatial estimate, only with moments and length given and spatial_below > 0, for a live P with
+   length_P < spatial_below; it reads the caller's inputs alone, never another pixel's estimate: a = b =
+   ws = 0; for dy = -3..3 (outer), dx = -3..3 (inner): Q = (x + dx, y + dy); skip Q if it lies outside
+   the image, is inert, (ident given) ident_Q != ident_P, or one of its two moments is not finite; else
+     w = 1.0f; normal given: atr_denoise's normal term, w = w * c; position term on: atr_denoise's
+     position term with pass 0's kp; skip Q unless w > 0; a = a + m_Q.x * w; b = b + m_Q.y * w; ws = ws
+     + w.
+   If ws > 0: m1 = a / ws, m2 = b / ws, e = m2 - m1*m1, e = e > 0 ? e : 0; lp = length_P > 0 ? length_P :
+   1; v = e * (float(spatial_below) / float(lp)) (SVGF's boost of short histories); else v stays.
+   Per-pass constant, on the host in f32: s = 1 << p; sp = sigma_position * float(s), kp = 1.0f / (sp *
+   sp). The position term is on iff position is given and sigma_position > 0, the luminance term iff
+   sigma_luminance > 0. There is no colour constant: the tolerance shrinks as the variance does.
+   Pass p (0 .. passes-1) for a live P, c_* and v_* the state at the start of the pass:
+     1. the variance under a 3 x 3 Gaussian at spacing 1 (not s): gs = ks = 0; for dy = -1..1 (outer),
+        dx = -1..1 (inner), over the Q inside the image, not inert and of P's ident: k = g[dy+1] *
+        g[dx+1], g = {0.25f, 0.5f, 0.25f}; gs = gs + v_Q * k; ks = ks + k. gv = gs / ks.
+     2. luminance term on: rl = 1.0f / (sigma_luminance * sqrtf(gv) + luminance_floor).
+     3. sum = 0,0,0, vs = 0, wsum = 0; the 25 taps in atr_denoise's order and under its skips (outside,
+        inert, another ident): w = h[dy+2] * h[dx+2]; atr_denoise's normal term; atr_denoise's position
+        term; luminance term on: x = fabsf(lum(c_Q) - lum(c_P)) * rl, w = w * (1.0f / (1.0f + x)); skip
+        Q unless w > 0; per channel sum = sum + c_Q * w; vs = vs + v_Q * (w * w); wsum = wsum + w.
+     4. if wsum > 0 the new colour is sum / wsum (three divisions) and the new variance vs / (wsum *
+        wsum), else both are kept.
+   The last pass's state is `out` and `variance_out`.
+   Asynchronous on `stream`; atr_render_wait covers it (tiles_done 0), atr_last_kernel_ms times it. No
+   scene is needed. The passes run in a grow-only workspace of their own, apart from atr_denoise's (the
+   two calls on two streams share nothing): 48 B per pixel, and 16 B more for each of normal and
+   position that is given; a call on another stream than the last first waits for it on the GPU.
+   ATR_E_INVALID, with nothing enqueued or written: ctx, params, color or variance NULL; out and
+   framebuffer both NULL; exactly one of moments and length given; width or height outside 1..16,384;
+   passes outside 1..8; normal_power_log2 outside 0..7; spatial_below outside 0..2^24; sigma_luminance
+   or sigma_position negative, NaN or infinite; luminance_floor not finite or not > 0; non-zero
+   reserved; a position term that is on whose kp is, in any of the passes, not finite and > 0.
+   atr_denoise_variance_check is that validation alone (without ctx), on the host, with no context and
+   no device: ATR_OK or ATR_E_INVALID. No struct and no ABI version change. */
+typedef struct {
+    int32_t passes;             /* 1..8; pass p (from 0) has tap spacing s = 2^p */
+    float   sigma_luminance;    /* >= 0, finite; 0: luminance term off */
+    float   luminance_floor;    /* > 0, finite: added to sigma_luminance * sd */
+    float   sigma_position;     /* as atr_denoise; ignored when position == NULL */
+    int32_t normal_power_log2;  /* 0..7, as atr_denoise */
+    int32_t spatial_below;      /* 0..2^24: histories shorter than this take the spatial estimate; 0: none do */
+    int32_t reserved[2];        /* must be 0 */
+} atr_denoise_variance_params;
+void atr_default_denoise_variance_params(atr_denoise_variance_params* out);   /* 3, 8.0f, 1e-4f, 0.0f, 5, 4, zeros */
+int atr_denoise_variance_check(const float* color, const float* variance, const atr_denoise_guides* guides,
+                               const float* moments, const uint32_t* length, int32_t width, int32_t height,
+                               const atr_denoise_variance_params* params, const float* out,
+                               const float* variance_out, const uint32_t* framebuffer);
+int atr_denoise_variance(atr_ctx* ctx, const float* color, const float* variance,
+                         const atr_denoise_guides* guides, const float* moments, const uint32_t* length,
+                         int32_t width, int32_t height, const atr_denoise_variance_params* params,
+                         float* out, float* variance_out, uint32_t* framebuffer, void* stream);
 
 /* wait_for_render_from_camera_to_finish: 1 = still running after timeout_ms, 0 = done,
    <0 = error. tiles_done (optional) = tiles of the last render known complete (progress). */
