@@ -3310,6 +3310,114 @@ int atr_accumulate(atr_ctx* c, const float* color, const atr_denoise_guides* gui
     return ATR_OK;
 } ATR_ABI_CATCH
 
+namespace {
+// A camera whose rays the camera calls can make (atray.h atr_camera_guides): a size, and every float
+// field finite. Host only.
+bool camera_rays_ok(const atr_camera& cm) {
+    if (cm.width < 1 || cm.height < 1 || cm.width > (1 << 16) || cm.height > (1 << 16)) return false;
+    const atr_vec3* v[5] = {&cm.camera_z, &cm.camera_x, &cm.camera_y, &cm.eye, &cm.frame_center};
+    for (const atr_vec3* a : v)
+        if (!std::isfinite(a->x) || !std::isfinite(a->y) || !std::isfinite(a->z)) return false;
+    return std::isfinite(cm.aspect_ratio) && std::isfinite(cm.h_fov) && std::isfinite(cm.half_pixel_width) &&
+           std::isfinite(cm.half_pixel_height);
+}
+
+int camera_rays_args(const atr_camera* cam, int64_t first_pixel, int64_t npixels, const float* origins,
+                     const float* directions) {
+    if (!cam || !camera_rays_ok(*cam)) return ATR_E_INVALID;
+    const int64_t total = int64_t(cam->width) * cam->height;
+    if (first_pixel < 0 || npixels < 0 || first_pixel > total || npixels > total - first_pixel) return ATR_E_INVALID;
+    if (npixels > 0 && (!origins || !directions)) return ATR_E_INVALID;
+    return ATR_OK;
+}
+}  // namespace
+
+// The primary rays of a range of pixels on the host (atray.h): guides.h's function, the one the
+// device kernels call.
+int atr_camera_rays_host(const atr_camera* cam, int64_t first_pixel, int64_t npixels, float* origins,
+                         float* directions) try {
+    const int rc = camera_rays_args(cam, first_pixel, npixels, origins, directions);
+    if (rc) return rc;
+    for (int64_t i = 0; i < npixels; ++i) {
+        const int64_t pix = first_pixel + i;
+        const V3 d = camera_ray_dir(*cam, int32_t(pix % cam->width), int32_t(pix / cam->width));
+        origins[3 * i] = cam->eye.x; origins[3 * i + 1] = cam->eye.y; origins[3 * i + 2] = cam->eye.z;
+        directions[3 * i] = d.x; directions[3 * i + 1] = d.y; directions[3 * i + 2] = d.z;
+    }
+    return ATR_OK;
+} ATR_ABI_CATCH
+
+// The same rays into device arrays (guides.hip camera_rays_kernel).
+int atr_camera_rays(atr_ctx* c, const atr_camera* cam, int64_t first_pixel, int64_t npixels, float* origins,
+                    float* directions, void* stream) try {
+    if (!c) return ATR_E_INVALID;
+    const int rc = camera_rays_args(cam, first_pixel, npixels, origins, directions);
+    if (rc || npixels == 0) return rc;
+    CameraRaysParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.cam = *cam;
+    P.first = first_pixel;
+    P.n = npixels;
+    P.o = origins;
+    P.d = directions;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = the null stream (HIP convention)
+    c->prog_active = false;
+    HIPCHK(hipEventRecord(c->ev_start, s));
+    HIPCHK(atr_launch_camera_rays(P, s));
+    HIPCHK(record_stop(c, s, nullptr));
+    HIPCHK(note_launch(c, s));
+    c->have_render = true;
+    c->last_stream = s;
+    c->last_ntiles = 0;
+    return ATR_OK;
+} ATR_ABI_CATCH
+
+// A camera's guides (atray.h): the render's block list for the tiles, one kernel
+// (guides.hip), no workspace.
+int atr_camera_guides(atr_ctx* c, const atr_camera* cam, const atr_tile* tiles, int32_t ntiles,
+                      const atr_guides_out* out, void* stream) try {
+    if (!c || !cam || !out || ntiles <= 0 || !tiles) return ATR_E_INVALID;
+    if (!out->normal && !out->position && !out->ident && !out->depth && !out->material) return ATR_E_INVALID;
+    if (!camera_rays_ok(*cam)) return ATR_E_INVALID;
+    for (int32_t i = 0; i < ntiles; ++i) {
+        const atr_tile& t = tiles[i];
+        if (t.min_x < 0 || t.min_y < 0 || t.max_x < t.min_x || t.max_y < t.min_y || t.max_x >= cam->width ||
+            t.max_y >= cam->height)
+            return ATR_E_INVALID;
+    }
+    if (!c->d_scene) return ATR_E_NOSCENE;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = the null stream (HIP convention)
+    int rc = ATR_OK;
+    BlockSet* bs = get_blocks(c, tiles, ntiles, cam->width, cam->height, rc);
+    if (!bs) return rc;
+    GuidesParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.cam = *cam;
+    P.scene = c->d_scene;
+    P.blocks = static_cast<const DBlock*>(bs->dev.p);  // the base list: no plan, its cost would train the render's
+    P.nblocks = int32_t(bs->host.size());
+    P.xcd_chunk = c->tune.xcd_chunk;
+    P.hyb_a = c->tune.hybrid_a;
+    P.hyb_b = c->tune.hybrid_b;
+    P.normal = out->normal;
+    P.position = out->position;
+    P.ident = out->ident;
+    P.depth = out->depth;
+    P.material = out->material;
+    P.error_flag = c->d_error;
+    c->prog_active = false;
+    HIPCHK(hipEventRecord(c->ev_start, s));
+    HIPCHK(atr_launch_camera_guides(P, s));
+    HIPCHK(record_stop(c, s, nullptr));
+    HIPCHK(note_launch(c, s));
+    c->have_render = true;
+    c->last_stream = s;
+    c->last_ntiles = 0;
+    return ATR_OK;
+} ATR_ABI_CATCH
+
 int atr_render_wait(atr_ctx* c, uint32_t timeout_ms, int32_t* tiles_done) try {
     if (!c) return ATR_E_INVALID;
     if (tiles_done) *tiles_done = 0;

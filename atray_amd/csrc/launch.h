@@ -7,6 +7,7 @@
 #include "denoise.h"
 #include "denoise_variance.h"
 #include "engine.h"
+#include "guides.h"
 #include "texels.h"
 
 extern "C" {
@@ -67,6 +68,9 @@ hipError_t atr_launch_denoise_variance_pass(const atr::DenoiseVarPass& P, int no
                                             hipStream_t s);
 // accumulate.hip
 hipError_t atr_launch_accumulate(const atr::AccumulateParams& P, hipStream_t s);
+// guides.hip
+hipError_t atr_launch_camera_guides(const atr::GuidesParams& P, hipStream_t s);
+hipError_t atr_launch_camera_rays(const atr::CameraRaysParams& P, hipStream_t s);
 // plan.hip
 hipError_t atr_launch_plan(const atr::DBlock* base, int32_t nb, unsigned long long* cost,
                            unsigned long long* cost_last, void* work, atr::DBlock* out, int32_t max_split,

@@ -133,6 +133,11 @@ class atr_denoise_guides(C.Structure):
     _fields_ = [("normal", C.c_void_p), ("position", C.c_void_p), ("ident", C.c_void_p)]
 
 
+class atr_guides_out(C.Structure):
+    _fields_ = [("normal", C.c_void_p), ("position", C.c_void_p), ("ident", C.c_void_p), ("depth", C.c_void_p),
+                ("material", C.c_void_p)]
+
+
 class atr_history(C.Structure):
     _fields_ = [("color", C.c_void_p), ("moments", C.c_void_p), ("length", C.c_void_p)]
 
@@ -181,6 +186,7 @@ EXPORTS = [
     "atr_render_sky_cells", "atr_scene_sky_record", "atr_sky_record_host",
     "atr_default_accumulate_params", "atr_accumulate_check", "atr_accumulate",
     "atr_default_denoise_variance_params", "atr_denoise_variance_check", "atr_denoise_variance",
+    "atr_camera_rays_host", "atr_camera_rays", "atr_camera_guides",
 ]
 # the diagnostic build's extra symbols (include/atray_diag.h; make -C atray_amd/csrc DIAG=1)
 DIAG_EXPORTS = ["atr_render_wave_trace", "atr_render_phase_clocks", "atr_render_path_counters",
@@ -257,6 +263,9 @@ def lib():
                                         P(atr_denoise_variance_params), vp, vp, vp], C.c_int),
         "atr_denoise_variance": ([vp, vp, vp, P(atr_denoise_guides), vp, vp, i32, i32,
                                   P(atr_denoise_variance_params), vp, vp, vp, vp], C.c_int),
+        "atr_camera_rays_host": ([P(atr_camera), i64, i64, vp, vp], C.c_int),
+        "atr_camera_rays": ([vp, P(atr_camera), i64, i64, vp, vp, vp], C.c_int),
+        "atr_camera_guides": ([vp, P(atr_camera), vp, i32, P(atr_guides_out), vp], C.c_int),
         "atr_render_packed_size": ([vp, i32], i64),
         "atr_render_counters": ([vp, P(atr_camera), vp, i32, C.c_uint64, i32, i64 * 10], C.c_int),
         "atr_render_cull_counters": ([vp, P(atr_camera), vp, i32, C.c_uint64, i32, i64 * 5], C.c_int),
@@ -619,6 +628,19 @@ def camera_rays(cam):
     inv = F(1.0) / np.sqrt(len2.astype(np.float64)).astype(F)
     dirs = np.ascontiguousarray(d * inv[:, None], F)
     return np.ascontiguousarray(np.broadcast_to(eye, dirs.shape), F), dirs
+
+
+def camera_rays_host(cam, first_pixel=0, npixels=None):
+    """atr_camera_rays_host: the primary rays of pixels first_pixel .. first_pixel + npixels - 1 of an
+    atr_camera (npixels None: to the last pixel), from the library's own generator -- the function the
+    device kernels call -- on the host, no device: (orig, dirs), (npixels, 3) float32 numpy arrays, the
+    bits of camera_rays(cam)[first_pixel:first_pixel + npixels]."""
+    first = int(first_pixel)
+    n = int(cam.width) * int(cam.height) - first if npixels is None else int(npixels)
+    orig, dirs = np.zeros((max(n, 0), 3), np.float32), np.zeros((max(n, 0), 3), np.float32)
+    check(lib().atr_camera_rays_host(C.byref(cam), first, n, orig.ctypes.data if orig.size else None,
+                                     dirs.ctypes.data if dirs.size else None), "camera rays host")
+    return orig, dirs
 
 
 class Engine:
@@ -1150,6 +1172,71 @@ class Engine:
         return (nrm.reshape(h, w, 3).contiguous(), pos.reshape(h, w, 3).contiguous(),
                 ident.to(torch.int32).reshape(h, w).contiguous())
 
+    _GUIDE_OUTPUTS = {"normal": ("float32", 3), "position": ("float32", 3), "ident": ("int32", 1),
+                      "depth": ("float32", 1), "material": ("int32", 1)}
+
+    def camera_guides(self, cam, tiles=None, outputs=("normal", "position", "ident"), out=None, stream=None):
+        """atr_camera_guides: the guides of a frame of `cam` in one device call, the bits render_guides
+        returns (atray.h has the formulas). tiles: (n, 4) inclusive rects inside the image, or None for
+        the full frame. outputs: any of "normal", "position" (H, W, 3) float32, "ident" (H, W) int32
+        (ATR_DENOISE_EMPTY is -1), "depth" (H, W) float32 (the hit's t), "material" (H, W) int32. out:
+        None for new tensors, or a dict of contiguous tensors of those shapes to write (ident and material
+        int32 or uint32); pixels outside the tiles keep what they hold (in a new tensor: undefined).
+        Enqueued on `stream` (a raw HIP stream), or torch's current one. Returns the tensors as a tuple in
+        the order of `outputs`; valid once the stream has run, e.g. after wait()."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        h, w = int(cam.height), int(cam.width)
+        outputs = tuple(outputs)
+        bad = [k for k in outputs if k not in self._GUIDE_OUTPUTS]
+        if bad or not outputs or len(set(outputs)) != len(outputs):
+            raise ValueError(f"outputs: a non-empty choice of {tuple(self._GUIDE_OUTPUTS)} is required")
+        given = dict(out) if out is not None else {}
+        extra = [k for k in given if k not in outputs]
+        if extra:
+            raise ValueError(f"out: entries {extra} are not among the outputs")
+        res = {}
+        for k in outputs:
+            dt, per = self._GUIDE_OUTPUTS[k]
+            shape = (h, w, per) if per > 1 else (h, w)
+            a = given.get(k)
+            if a is None:
+                a = torch.empty(shape, dtype=getattr(torch, dt), device=dev)
+            else:
+                kinds = (getattr(torch, dt),) + ((torch.uint32,) if dt == "int32" and hasattr(torch, "uint32") else ())
+                if (not isinstance(a, torch.Tensor) or a.dtype not in kinds or tuple(a.shape) != shape
+                        or a.device != dev or not a.is_contiguous()):
+                    raise ValueError(f"out[{k!r}]: a contiguous {shape} {dt} tensor on {dev} is required")
+            res[k] = a
+        if tiles is None:
+            tiles = [[0, 0, w - 1, h - 1]]
+        arr, n = tiles if isinstance(tiles, tuple) else tiles_array(tiles)
+        g = atr_guides_out(*[res[k].data_ptr() if k in res else None
+                             for k in ("normal", "position", "ident", "depth", "material")])
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        check(lib().atr_camera_guides(self.h, C.byref(cam), C.cast(arr, C.c_void_p), n, C.byref(g),
+                                      C.c_void_p(stream) if stream else None), "camera guides")
+        return tuple(res[k] for k in outputs)
+
+    def camera_rays(self, cam, first_pixel=0, npixels=None, stream=None):
+        """atr_camera_rays: the primary rays of pixels first_pixel .. first_pixel + npixels - 1 of `cam`
+        (npixels None: to the last pixel) made on the device: (orig, dirs), (npixels, 3) float32 tensors,
+        the bits of camera_rays(cam) -- input for trace_rays and radiance_rays without a host build or a
+        copy. Enqueued on `stream` (a raw HIP stream), or torch's current one."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        first = int(first_pixel)
+        n = int(cam.width) * int(cam.height) - first if npixels is None else int(npixels)
+        orig = torch.empty((max(n, 0), 3), dtype=torch.float32, device=dev)
+        dirs = torch.empty((max(n, 0), 3), dtype=torch.float32, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        check(lib().atr_camera_rays(self.h, C.byref(cam), first, n, C.c_void_p(orig.data_ptr()) if n > 0 else None,
+                                    C.c_void_p(dirs.data_ptr()) if n > 0 else None,
+                                    C.c_void_p(stream) if stream else None), "camera rays")
+        return orig, dirs
+
     def accumulate(self, color, guides, prev=None, cam=None, alpha=0.0, alpha_moments=0.0, max_length=64,
                    plane_tolerance=0.02, min_normal_dot=0.9, moments=True, out=None, variance=False, framebuffer=False,
                    stream=None):
@@ -1597,12 +1684,12 @@ class TemporalAccumulator:
 
     def push(self, cam, color, guides=None, stream=None):
         """One frame: `color` (H, W, 3) float32 as rendered from `cam`, guides (normal, position, ident)
-        or None for render_guides(cam). Returns (accumulated (H, W, 3), variance (H, W)); the accumulated
-        tensor belongs to the history and is overwritten by the push after the next. On torch's current
-        stream, or `stream` if the guides are supplied."""
+        or None for camera_guides(cam) (the bits of render_guides(cam), made in one device call). Returns
+        (accumulated (H, W, 3), variance (H, W)); the accumulated tensor belongs to the history and is
+        overwritten by the push after the next. On `stream` (a raw HIP stream), or torch's current one."""
         import torch
         if guides is None:
-            guides = self.engine.render_guides(cam, stream=stream)
+            guides = self.engine.camera_guides(cam, stream=stream)
         h, w = int(color.shape[0]), int(color.shape[1])
         if self.prev is not None and tuple(self.prev["color"].shape[:2]) != (h, w):
             self.prev = None

@@ -33,7 +33,7 @@ extern "C" {
    atr_default_denoise_params likewise; atr_accumulate, atr_accumulate_check, atr_history,
    atr_accumulate_params and atr_default_accumulate_params likewise; atr_denoise_variance,
    atr_denoise_variance_check, atr_denoise_variance_params and atr_default_denoise_variance_params
-   likewise. */
+   likewise; atr_camera_guides, atr_guides_out, atr_camera_rays and atr_camera_rays_host likewise. */
 #define ATR_ABI_VERSION 2
 
 enum {
@@ -1092,6 +1092,52 @@ int atr_denoise_variance(atr_ctx* ctx, const float* color, const float* variance
                          const atr_denoise_guides* guides, const float* moments, const uint32_t* length,
                          int32_t width, int32_t height, const atr_denoise_variance_params* params,
                          float* out, float* variance_out, uint32_t* framebuffer, void* stream);
+
+/* ---------------------------------------------------------------- a camera's rays and guides
+   The primary ray of pixel (x, y) of a camera, as atr_render_start_ex casts it without anti-aliasing
+   (every step a separately rounded f32 operation):
+     film_y = -1 + 2 * (y / height);  film_x = ((-1 + 2 * (x / width)) * h_fov) * aspect_ratio;
+     origin = eye;  direction = unit((frame_center + camera_x * film_x) + camera_y * film_y - eye).
+   It goes through the pixel's centre whatever cam->anti_aliasing says; samples_per_pixel and
+   bounce_limit are not read. A camera is accepted when width and height are 1..65,536 and every float
+   field is finite (ATR_E_INVALID otherwise, checked on the host before anything is enqueued).
+
+   atr_camera_rays_host: the rays of pixels first_pixel .. first_pixel + npixels - 1 in pixel order
+   (pixel p = (p % width, p / width)), 3 floats each, into HOST arrays; no context. atr_camera_rays: the
+   same bits into DEVICE arrays, asynchronous on `stream`; ready-made input for atr_trace_rays and
+   atr_radiance_rays (ray_base = first_pixel re-renders that range of pixels). ATR_E_INVALID for a
+   range outside [0, width * height] or NULL outputs with npixels > 0; npixels == 0 is ATR_OK. */
+int atr_camera_rays_host(const atr_camera* cam, int64_t first_pixel, int64_t npixels, float* origins,
+                         float* directions);
+int atr_camera_rays(atr_ctx* ctx, const atr_camera* cam, int64_t first_pixel, int64_t npixels,
+                    float* origins, float* directions, void* stream);
+
+/* atr_camera_guides: the guides atr_denoise, atr_accumulate and atr_denoise_variance read, for the
+   pixels of `tiles` (inclusive rects inside the image; a pixel in overlapping tiles is done once;
+   pixels outside them are not written), in one kernel: the pixel's ray above is tested as
+   atr_trace_rays tests a caller's ray (a failing ray is not traced: kind ATR_RAY_INVALID), traced to
+   atr_trace_rays' closest hit, and
+     depth    = that hit's t (3.402823466e38: none);   material = its material (0: sky, invalid);
+     position = eye + direction * t (a multiply, then an add, each rounded; with the t above on sky
+                and invalid pixels);
+     normal   = the hit's unit normal n, negated where (-d.x * n.x + -d.y * n.y) + -d.z * n.z < 0 (the
+                bounce's convention); +0, 0, 0 on sky and invalid pixels;
+     ident    = ATR_DENOISE_EMPTY on sky and invalid pixels, else (kind << 28) | (model + 1) with
+                atr_trace_rays' kind and model (model + 1 = 0 for a sphere or a plane).
+   Every value equals, bit for bit, what atr_trace_rays on atr_camera_rays' rays followed by that
+   arithmetic gives. Asynchronous on `stream`; atr_render_wait covers it (tiles_done 0,
+   ATR_E_TREE_DEPTH as for a render) and atr_last_kernel_ms times it; no workspace. ATR_E_INVALID: ctx,
+   cam or out NULL, all five outputs NULL, ntiles <= 0 or tiles NULL, a tile outside the image or
+   empty, a camera that is not accepted (above). ATR_E_NOSCENE before atr_scene_upload. */
+typedef struct {            /* DEVICE pointers, IMAGE layout (pixel (x,y) at y*width + x); any may be NULL */
+    float*    normal;       /* 3 per pixel */
+    float*    position;     /* 3 per pixel */
+    uint32_t* ident;
+    float*    depth;
+    int32_t*  material;
+} atr_guides_out;
+int atr_camera_guides(atr_ctx* ctx, const atr_camera* cam, const atr_tile* tiles, int32_t ntiles,
+                      const atr_guides_out* out, void* stream);
 
 /* wait_for_render_from_camera_to_finish: 1 = still running after timeout_ms, 0 = done,
    <0 = error. tiles_done (optional) = tiles of the last render known complete (progress). */

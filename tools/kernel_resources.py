@@ -1,8 +1,10 @@
-"""(VGPRs, SGPRs, scratch bytes, LDS bytes, spilled dwords) of every kernel of render.s and paths.s in
-two `make -C atray_amd/csrc asm` output directories, side by side, with the kernels that differ marked:
-the table a change to the kernels commits as profiles/rNN/kernel_resources.txt.
+"""(VGPRs, SGPRs, scratch bytes, LDS bytes, spilled dwords) of every kernel of render.s, paths.s and
+guides.s in two `make -C atray_amd/csrc asm` output directories, side by side, with the kernels that differ
+marked (a file one directory lacks counts as empty): the table a change to the kernels commits as
+profiles/rNN/kernel_resources.txt.
 
     python tools/kernel_resources.py PARENT_ASM_DIR THIS_ASM_DIR > profiles/rNN/kernel_resources.txt"""
+import os
 import re
 import subprocess
 import sys
@@ -10,6 +12,8 @@ import sys
 
 def table(path):
     out = {}
+    if not os.path.exists(path):
+        return out
     for blk in open(path).read().split("- .agpr_count:")[1:]:
         def g(k):
             m = re.search(r"\." + k + r":\s+(\S+)", blk)
@@ -20,7 +24,7 @@ def table(path):
 
 
 pa, ch = sys.argv[1], sys.argv[2]
-for f in ["render.s", "paths.s"]:
+for f in ["render.s", "paths.s", "guides.s"]:
     print("# " + f)
     a, b = table(pa + "/" + f), table(ch + "/" + f)
     names = list(b)
