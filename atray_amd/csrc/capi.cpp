@@ -2308,6 +2308,134 @@ int atr_gather_radiance(atr_ctx* c, const float* points, const float* normals, i
     return ATR_OK;
 } ATR_ABI_CATCH
 
+// Light probes as L2 spherical harmonics (atray.h): atr_gather_radiance's flow on points
+// without normals -- batches of whole probes, the entry kernel and the per-probe resolve of
+// probe_sh.hip around the engine's own bounce levels; the workspace is obtained before anything is
+// enqueued and there is no cell-kernel fallback.
+int atr_probe_sh(atr_ctx* c, const float* points, int64_t npoints, int32_t nsamples, uint32_t first_sample,
+                 int64_t point_base, int32_t bounce_limit, uint64_t seed, const atr_probe_sh_out* out,
+                 int32_t sort_bits, void* stream) try {
+    if (!c) return ATR_E_INVALID;
+    if (npoints < 0 || npoints >= (int64_t(1) << 31) || nsamples < 1 || nsamples > 65536) return ATR_E_INVALID;
+    if (npoints * int64_t(nsamples) >= (int64_t(1) << 31)) return ATR_E_INVALID;
+    // the stream hash shifts the sample index by 40 bits, and float(first_sample + nsamples) is exact up to 2^24
+    if (uint64_t(first_sample) + uint64_t(nsamples) > (uint64_t(1) << 24)) return ATR_E_INVALID;
+    // the queues carry the stream index in 32 bits
+    if (point_base < 0 || point_base > (int64_t(1) << 32) - npoints) return ATR_E_INVALID;
+    if (bounce_limit < 1 || bounce_limit > kMaxPathBounces) return ATR_E_INVALID;
+    if (sort_bits != -1 && sort_bits != 0 && (sort_bits < 2 || sort_bits > kMaxSortBits)) return ATR_E_INVALID;
+    if (npoints > 0 && (!out || !points)) return ATR_E_INVALID;
+    if (out && first_sample > 0 && !out->sum) return ATR_E_INVALID;
+    if (npoints > 0 && !out->sh && !out->sum && !out->ray_casts && !out->invalid && !out->sample_rgb && !out->dirs &&
+        !out->traced_rays)
+        return ATR_E_INVALID;
+    if (!c->d_scene) return ATR_E_NOSCENE;
+    if (npoints == 0) return ATR_OK;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // the order is of the bounce levels' queues: without a second level there is nothing to order
+    int32_t bits = clamp_sort_bits(bounce_limit >= 2 ? (sort_bits < 0 ? c->tune.path_sort_bits : sort_bits) : 0);
+    atr_ctx::PathWS* ws = nullptr;
+    int64_t per_batch = 0;  // probes
+    HIPCHK(path_batches(c, s, nsamples, npoints, bounce_limit, std::min(16, c->tune.path_batch_log2), false, bits, ws,
+                        per_batch));
+    PathParams Q;
+    std::memset(&Q, 0, sizeof(Q));
+    Q.cam.bounce_limit = bounce_limit;
+    Q.cam.samples_per_pixel = uint32_t(nsamples);
+    Q.scene = c->d_scene;
+    Q.seed = seed;
+    Q.error_flag = c->d_error;
+    Q.hyb_a = c->tune.hybrid_a;
+    Q.hyb_b = c->tune.hybrid_b;
+    bind_path_workspace(c, ws, bits, Q);
+    ProbeShParams R;
+    std::memset(&R, 0, sizeof(R));
+    R.scene = Q.scene;
+    R.p = points;
+    R.nsamples = uint32_t(nsamples);
+    R.first_sample = first_sample;
+    R.bounce_limit = bounce_limit;
+    R.hyb_a = Q.hyb_a;
+    R.hyb_b = Q.hyb_b;
+    R.point_base = point_base;
+    R.seed = seed;
+    R.q0 = Q.q[0];
+    R.cap = Q.cap;
+    R.out = Q.out;
+    R.ctl = Q.ctl;
+    R.sort = Q.sort;
+    R.error_flag = Q.error_flag;
+    R.sh = out->sh;
+    R.sum = out->sum;
+    R.ray_casts = out->ray_casts;
+    R.invalid = out->invalid;
+    R.sample_rgb = out->sample_rgb;
+    R.dirs = out->dirs;
+    c->prog_active = false;
+    HIPCHK(hipEventRecord(c->ev_start, s));
+    hipEvent_t done = nullptr;
+    int k = -1;
+    if (out->traced_rays) {
+        HIPCHK(ring_take(c, s, k, Q.traced_rays));
+        R.traced_rays = Q.traced_rays;
+    }
+    for (int64_t p0 = 0; p0 < npoints; p0 += per_batch) {  // whole probes
+        const int64_t np = std::min<int64_t>(per_batch, npoints - p0);
+        Q.ncells = int32_t(np);
+        R.point0 = uint32_t(p0);
+        R.npoints = uint32_t(np);
+        R.n = uint32_t(np * int64_t(nsamples));
+        HIPCHK(reset_path_batch(Q, bounce_limit, bits, s));
+        HIPCHK(atr_launch_probe_sh_entry(R, c->ncu, s));
+        HIPCHK(launch_bounce_levels(c, Q, bounce_limit, bits, s));
+        HIPCHK(atr_launch_probe_sh_resolve(R, s));
+    }
+    if (k >= 0) {
+        HIPCHK(atr_launch_traced_finish(Q.traced_rays, out->traced_rays, s));
+        HIPCHK(ring_done(c, s, k));
+        done = c->tev[k];
+    }
+    HIPCHK(hipEventRecord(ws->ev, s));
+    HIPCHK(record_stop(c, s, done));
+    HIPCHK(note_launch(c, s, c->ev_last != c->ev_stop));  // a ring event covers it
+    c->have_render = true;
+    c->last_stream = s;
+    c->last_ntiles = 0;
+    return ATR_OK;
+} ATR_ABI_CATCH
+
+// The probes' sampler and basis on the host (atray.h): the kernels' own functions (engine.h), compiled
+// with the library's -ffp-contract=off. No device, no context.
+int atr_probe_directions(int64_t npoints, int32_t nsamples, uint32_t first_sample, int64_t point_base, uint64_t seed,
+                         float* dirs_out, uint8_t* tries_out) try {
+    if (npoints < 0 || npoints >= (int64_t(1) << 31) || nsamples < 1 || nsamples > 65536) return ATR_E_INVALID;
+    if (npoints * int64_t(nsamples) >= (int64_t(1) << 31)) return ATR_E_INVALID;
+    if (uint64_t(first_sample) + uint64_t(nsamples) > (uint64_t(1) << 24)) return ATR_E_INVALID;
+    if (point_base < 0 || point_base > (int64_t(1) << 32) - npoints) return ATR_E_INVALID;
+    for (int64_t i = 0; i < npoints; ++i) {
+        for (int32_t s = 0; s < nsamples; ++s) {
+            const int64_t k = i * nsamples + s;
+            uint64_t st, stream;
+            uint32_t tries;
+            const V3 d = probe_dir_state(seed, point_base + i, first_sample + uint32_t(s), st, stream, tries);
+            if (dirs_out) {
+                dirs_out[3 * k] = d.x;
+                dirs_out[3 * k + 1] = d.y;
+                dirs_out[3 * k + 2] = d.z;
+            }
+            if (tries_out) tries_out[k] = uint8_t(tries);
+        }
+    }
+    return ATR_OK;
+} ATR_ABI_CATCH
+
+int atr_sh_basis(const float* dirs, int64_t n, float* basis_out) try {
+    if (n < 0 || (n > 0 && (!dirs || !basis_out))) return ATR_E_INVALID;
+    for (int64_t i = 0; i < n; ++i) sh_basis(mk(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]), basis_out + 9 * i);
+    return ATR_OK;
+} ATR_ABI_CATCH
+
 int atr_render_adaptive_info(atr_ctx* c, int64_t info_out[4]) try {
     if (!c || !info_out || c->adapt_last < 0) return ATR_E_INVALID;
     HIPCHK(hipSetDevice(c->device));

@@ -524,6 +524,80 @@ ATR_HD V3 gather_dir_state(uint64_t seed, int64_t point, uint32_t sample, V3 n, 
     return unit(add(mk(r0, r1, r2), n));
 }
 
+// A light-probe batch (atr_probe_sh, probe_sh.hip): GatherRadianceParams without the
+// normals and with 27 sums per probe. [point0, point0 + npoints) of the array p, nsamples samples each;
+// item i * nsamples + s is sample first_sample + s of probe point_base + point0 + i and owns result
+// slot i * nsamples + s. The entry kernel draws the direction over the whole sphere on the item's
+// stream (probe_dir_state below), traces it and finishes the path in its slot or appends it to queue
+// 0; every sample of a valid probe is traced, so a slot holds a finished path's {colour, casts} or,
+// for every item of an invalid probe, kRayInvalid. The resolve (a wave per probe) draws each slot's
+// direction again, evaluates the nine basis functions on it (sh_basis) and adds colour x basis in
+// sample order into the 27 sums (index 3 k + c); a null output is not written.
+struct ProbeShParams {
+    const DScene* scene;
+    const float* p;        // 3 per probe of the call
+    uint32_t point0, npoints;
+    uint32_t n;            // npoints x nsamples (< 2^31)
+    uint32_t nsamples, first_sample;
+    int32_t bounce_limit;
+    int32_t hyb_a, hyb_b;
+    int64_t point_base;
+    uint64_t seed;
+    float4_t* q0;     // queue 0 of the workspace (PathParams::q[0])
+    int64_t cap;
+    float4_t* out;    // the result slots (PathParams::out)
+    PathCtl* ctl;
+    PathSort sort;
+    unsigned long long* traced_rays;  // 64 spread counters (a ring slot), or null
+    int32_t* error_flag;
+    float* sh;             // 27 per probe
+    float* sum;            // 27 per probe
+    uint32_t* ray_casts;
+    uint8_t* invalid;
+    float* sample_rgb;     // 3 per item of the call
+    float* dirs;           // 3 per item of the call
+};
+
+// Sample `sample` of probe `point`: a direction uniform over the sphere, on the (pixel, sample) stream
+// of path_stream, by rejection inside the radial shell 2^-10 <= |v|^2 <= 1 of the cube's draws -- no
+// sine or cosine, so the host and the device make the same bits. At most kProbeTries tries of three
+// rand_bi draws each; the first one inside the shell is normalised as unit() does. If none is (about
+// 1e-10 per sample), the direction is +z: the loop has a fixed end on every lane. The stream comes
+// back as the draws left it. `tries` = the accepted try, 1-based, or kProbeTries + 1. No operation in
+// the loop crosses lanes, so lanes of a wave may leave it at different trips.
+constexpr int kProbeTries = 32;
+constexpr float kProbeLen2Min = 0.0009765625f;  // 0x1p-10f
+ATR_HD V3 probe_dir_state(uint64_t seed, int64_t point, uint32_t sample, uint64_t& st, uint64_t& stream,
+                          uint32_t& tries) {
+    path_stream(seed, point, sample, st, stream);
+    for (int t = 1; t <= kProbeTries; ++t) {
+        const float r0 = rand_bi(st, stream);
+        const float r1 = rand_bi(st, stream);
+        const float r2 = rand_bi(st, stream);
+        const float l2 = (r0 * r0 + r1 * r1) + r2 * r2;
+        if (kProbeLen2Min <= l2 && l2 <= 1.0f) {
+            tries = uint32_t(t);
+            return scale(mk(r0, r1, r2), 1.0f / sqrtf(l2));
+        }
+    }
+    tries = uint32_t(kProbeTries) + 1u;
+    return mk(0.f, 0.f, 1.f);
+}
+
+// The nine real spherical harmonics of bands 0..2 on a unit direction (atray.h atr_probe_sh), each
+// product separately rounded in this order.
+ATR_HD void sh_basis(V3 d, float y[9]) {
+    y[0] = 0.282094792f;
+    y[1] = 0.488602512f * d.y;
+    y[2] = 0.488602512f * d.z;
+    y[3] = 0.488602512f * d.x;
+    y[4] = 1.092548431f * (d.x * d.y);
+    y[5] = 1.092548431f * (d.y * d.z);
+    y[6] = 0.315391565f * ((3.0f * (d.z * d.z)) - 1.0f);
+    y[7] = 1.092548431f * (d.x * d.z);
+    y[8] = 0.546274215f * ((d.x * d.x) - (d.y * d.y));
+}
+
 // The validity test of a caller's ray (atray.h atr_trace_rays): six finite inputs and a direction
 // normalised to within 2^-20 in len2 (what unit() leaves is within 6 x 2^-24). The comparisons are
 // false for a NaN, and an infinite component fails the first one.

@@ -49,6 +49,9 @@ hipError_t atr_launch_radiance_resolve(const atr::RadianceParams& P, hipStream_t
 // gather_radiance.hip
 hipError_t atr_launch_gather_radiance_entry(const atr::GatherRadianceParams& P, int ncu, hipStream_t s);
 hipError_t atr_launch_gather_radiance_resolve(const atr::GatherRadianceParams& P, hipStream_t s);
+// probe_sh.hip
+hipError_t atr_launch_probe_sh_entry(const atr::ProbeShParams& P, int ncu, hipStream_t s);
+hipError_t atr_launch_probe_sh_resolve(const atr::ProbeShParams& P, hipStream_t s);
 // texels.hip
 hipError_t atr_launch_texel_classify(const atr::TexelParams& P, hipStream_t s);
 hipError_t atr_launch_texel_big(const atr::TexelParams& P, uint32_t nbig, hipStream_t s);

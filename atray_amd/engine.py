@@ -119,6 +119,11 @@ class atr_gather_radiance_out(C.Structure):
                 ("traced_rays", C.c_void_p)]
 
 
+class atr_probe_sh_out(C.Structure):
+    _fields_ = [("sh", C.c_void_p), ("sum", C.c_void_p), ("ray_casts", C.c_void_p), ("invalid", C.c_void_p),
+                ("sample_rgb", C.c_void_p), ("dirs", C.c_void_p), ("traced_rays", C.c_void_p)]
+
+
 class atr_texels_out(C.Structure):
     _fields_ = [("slot", C.c_void_p), ("texel", C.c_void_p), ("face", C.c_void_p), ("bary", C.c_void_p),
                 ("point", C.c_void_p), ("normal", C.c_void_p)]
@@ -187,6 +192,7 @@ EXPORTS = [
     "atr_default_accumulate_params", "atr_accumulate_check", "atr_accumulate",
     "atr_default_denoise_variance_params", "atr_denoise_variance_check", "atr_denoise_variance",
     "atr_camera_rays_host", "atr_camera_rays", "atr_camera_guides",
+    "atr_probe_sh", "atr_probe_directions", "atr_sh_basis",
 ]
 # the diagnostic build's extra symbols (include/atray_diag.h; make -C atray_amd/csrc DIAG=1)
 DIAG_EXPORTS = ["atr_render_wave_trace", "atr_render_phase_clocks", "atr_render_path_counters",
@@ -249,6 +255,9 @@ def lib():
                               C.c_int),
         "atr_gather_radiance": ([vp, vp, vp, i64, i32, u32, i64, i32, C.c_uint64, P(atr_gather_radiance_out), i32,
                                  vp], C.c_int),
+        "atr_probe_sh": ([vp, vp, i64, i32, u32, i64, i32, C.c_uint64, P(atr_probe_sh_out), i32, vp], C.c_int),
+        "atr_probe_directions": ([i64, i32, u32, i64, C.c_uint64, vp, vp], C.c_int),
+        "atr_sh_basis": ([vp, i64, vp], C.c_int),
         "atr_mesh_texels": ([vp, vp, i32, i32, i32, i64, P(atr_texels_out), P(i64), vp], C.c_int),
         "atr_texels_to_image": ([vp, vp, vp, i64, i32, i32, i32, C.c_float * 3, vp, vp], C.c_int),
         "atr_default_denoise_params": ([P(atr_denoise_params)], None),
@@ -586,6 +595,69 @@ def gather_directions(normals, nsamples, first_sample=0, point_base=0, seed=0):
                                       C.c_uint64(int(seed) & (2**64 - 1)), dirs.ctypes.data if dirs.size else None,
                                       traced.ctypes.data if traced.size else None), "gather directions")
     return dirs, traced
+
+
+def probe_directions(npoints, nsamples, first_sample=0, point_base=0, seed=0):
+    """atr_probe_directions: the light probes' sphere sampler on the host, no device. Returns (dirs
+    (npoints, nsamples, 3) float32, tries (npoints, nsamples) uint8): the direction of every (probe,
+    sample), the bits probe_sh's dirs holds for a valid probe, and the try that was accepted (1..32, or
+    33 where all 32 failed and the direction is +z)."""
+    n, ns = int(npoints), int(nsamples)
+    dirs = np.zeros((max(n, 0), max(ns, 0), 3), np.float32)
+    tries = np.zeros((max(n, 0), max(ns, 0)), np.uint8)
+    check(lib().atr_probe_directions(n, ns, int(first_sample), int(point_base), C.c_uint64(int(seed) & (2**64 - 1)),
+                                     dirs.ctypes.data if dirs.size else None,
+                                     tries.ctypes.data if tries.size else None), "probe directions")
+    return dirs, tries
+
+
+def sh_basis(dirs):
+    """atr_sh_basis: the nine real spherical harmonics of bands 0..2 on unit directions, in the device's
+    f32 operation order. dirs: (..., 3) float32 (numpy, or anything numpy converts). Returns (..., 9)
+    float32."""
+    d = np.ascontiguousarray(dirs, np.float32)
+    if d.ndim < 1 or d.shape[-1] != 3:
+        raise ValueError("dirs: an (..., 3) float32 array is required")
+    out = np.zeros(d.shape[:-1] + (9,), np.float32)
+    n = out.size // 9
+    check(lib().atr_sh_basis(d.ctypes.data if n else None, n, out.ctypes.data if n else None), "sh basis")
+    return out
+
+
+def probe_grid(lo, hi, counts):
+    """The probe points of a regular grid: counts = (nx, ny, nz) points per axis from lo to hi inclusive
+    (an axis with one point sits at the middle of its range), x fastest, then y, then z. Returns
+    (nx * ny * nz, 3) float32."""
+    lo, hi = np.asarray(lo, np.float64).reshape(3), np.asarray(hi, np.float64).reshape(3)
+    counts = tuple(int(c) for c in counts)
+    if len(counts) != 3 or min(counts) < 1:
+        raise ValueError("counts: three positive integers are required")
+    axes = [np.linspace(lo[a], hi[a], counts[a]) if counts[a] > 1 else np.array([(lo[a] + hi[a]) * 0.5])
+            for a in range(3)]
+    z, y, x = np.meshgrid(axes[2], axes[1], axes[0], indexing="ij")
+    return np.stack([x.ravel(), y.ravel(), z.ravel()], axis=1).astype(np.float32)
+
+
+# the cosine lobe's zonal factors for bands 0, 1, 2 (Ramamoorthi and Hanrahan 2001), per coefficient
+_SH_COSINE = np.array([np.pi] + [2.0 * np.pi / 3.0] * 3 + [np.pi / 4.0] * 5, np.float32)
+
+
+def sh_irradiance(sh, normals):
+    """The Lambertian irradiance that probe coefficients give a surface with unit normal n: the
+    projected radiance convolved with the clamped cosine lobe, E(n) = sum_k A_k sh[k] Y_k(n) with A =
+    pi, 2 pi / 3 and pi / 4 for bands 0, 1 and 2, in numpy float32. sh: (..., 9, 3) (probe_sh's sh
+    viewed as coefficient x channel); normals: (m, 3). Returns (..., m, 3). This is the irradiance of
+    the band-limited radiance -- a constant radiance L gives pi L for every normal -- and not
+    gather_radiance's mean, which weights directions by the renderer's own bounce sampler and not by
+    the cosine."""
+    sh = np.asarray(sh, np.float32)
+    if sh.ndim < 2 or sh.shape[-2:] != (9, 3):
+        raise ValueError("sh: an (..., 9, 3) float32 array is required")
+    y = sh_basis(normals)
+    if y.ndim != 2:
+        raise ValueError("normals: an (m, 3) float32 array is required")
+    w = (y * _SH_COSINE[None, :]).astype(np.float32)  # (m, 9)
+    return np.einsum("mk,...kc->...mc", w, sh).astype(np.float32)
 
 
 def surface_points(orig, dirs, t, normal):
@@ -994,6 +1066,70 @@ class Engine:
                                         int(point_base), int(bounces), C.c_uint64(int(seed) & (2**64 - 1)),
                                         C.byref(go), int(sort_bits), C.c_void_p(stream) if stream else None),
               "gather radiance")
+        return out, traced
+
+    # atr_probe_sh_out outputs: name -> (torch dtype name, trailing shape; "s" = nsamples)
+    _PROBE_SH_OUTPUTS = {"sh": ("float32", (9, 3)), "sum": ("float32", (9, 3)), "ray_casts": ("int32", ()),
+                         "invalid": ("uint8", ()), "sample_rgb": ("float32", ("s", 3)),
+                         "dirs": ("float32", ("s", 3))}
+
+    def probe_sh(self, points, nsamples, bounces, seed=0, first_sample=0, point_base=0, start=None,
+                 want=("sh", "invalid"), sort_bits=-1, stream=None):
+        """atr_probe_sh: light probes -- the radiance arriving at every point over the whole sphere,
+        nsamples paths per probe (the direction drawn uniformly on the device on the stream of (seed,
+        point_base + i, first_sample + s), then at most `bounces` bounces on that stream), projected
+        on the nine real spherical harmonics of bands 0..2. points: a contiguous (n, 3) float32 tensor
+        on the engine's device (a point that is not finite comes back with invalid 1, untraced).
+        `want` names the outputs: sh, sum (n, 9, 3) float32 (coefficient, channel); ray_casts (n,)
+        int32; invalid (n,) uint8; sample_rgb, dirs (n, nsamples, 3) float32. A later sample range
+        continues an earlier one through `start`, a dict with that call's `sum` tensor (required when
+        first_sample > 0) and optionally its `ray_casts`; they are updated in place and returned.
+        Enqueued on `stream` (a raw HIP stream), or torch's current one. Returns ({name: tensor}, the
+        traced-ray count as a one-element int64 tensor); valid once the stream has run, e.g. after
+        wait(). sh_irradiance(sh, normals) lights a normal from the result."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if not isinstance(points, torch.Tensor) or points.dtype != torch.float32 or points.dim() != 2 \
+                or points.shape[1] != 3:
+            raise ValueError("points: an (n, 3) float32 tensor is required")
+        if points.device != dev:
+            raise ValueError(f"points: not on {dev}")
+        if not points.is_contiguous():
+            raise ValueError("points: not contiguous")
+        bad = [k for k in want if k not in self._PROBE_SH_OUTPUTS]
+        if bad:
+            raise ValueError(f"unknown outputs {bad}")
+        n, ns = int(points.shape[0]), int(nsamples)
+        if not 1 <= ns <= 65536:
+            raise ValueError("nsamples: 1..65536")
+
+        def shape(k):
+            return (n,) + tuple(ns if d == "s" else d for d in self._PROBE_SH_OUTPUTS[k][1])
+
+        given = dict(start or {})
+        bad = [k for k in given if k not in ("sum", "ray_casts")]
+        if bad:
+            raise ValueError(f"start: unknown entries {bad}")
+        for k, a in given.items():
+            dt = self._PROBE_SH_OUTPUTS[k][0]
+            if (not isinstance(a, torch.Tensor) or a.dtype != getattr(torch, dt) or a.device != dev
+                    or not a.is_contiguous() or tuple(a.shape) != shape(k)):
+                raise ValueError(f"start[{k!r}]: a contiguous {dt} tensor of {n} probes on {dev} is required")
+        if int(first_sample) > 0 and "sum" not in given:
+            raise ValueError("start: sum is required when first_sample > 0")
+        out = {}
+        for k in tuple(want) + tuple(k for k in given if k not in want):
+            out[k] = given[k] if k in given else torch.empty(
+                shape(k), dtype=getattr(torch, self._PROBE_SH_OUTPUTS[k][0]), device=dev)
+        traced = torch.zeros(1, dtype=torch.int64, device=dev)
+        go = atr_probe_sh_out(*[out[k].data_ptr() if k in out and n else None
+                                for k in ("sh", "sum", "ray_casts", "invalid", "sample_rgb", "dirs")],
+                              traced.data_ptr())
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        check(lib().atr_probe_sh(self.h, C.c_void_p(points.data_ptr()) if n else None, n, ns, int(first_sample),
+                                 int(point_base), int(bounces), C.c_uint64(int(seed) & (2**64 - 1)), C.byref(go),
+                                 int(sort_bits), C.c_void_p(stream) if stream else None), "probe sh")
         return out, traced
 
     # atr_texels_out outputs: name -> (torch dtype name, trailing shape); slot is per texel, the rest per covered k

@@ -33,7 +33,8 @@ extern "C" {
    atr_default_denoise_params likewise; atr_accumulate, atr_accumulate_check, atr_history,
    atr_accumulate_params and atr_default_accumulate_params likewise; atr_denoise_variance,
    atr_denoise_variance_check, atr_denoise_variance_params and atr_default_denoise_variance_params
-   likewise; atr_camera_guides, atr_guides_out, atr_camera_rays and atr_camera_rays_host likewise. */
+   likewise; atr_camera_guides, atr_guides_out, atr_camera_rays and atr_camera_rays_host likewise;
+   atr_probe_sh, atr_probe_sh_out, atr_probe_directions and atr_sh_basis likewise. */
 #define ATR_ABI_VERSION 2
 
 enum {
@@ -806,6 +807,86 @@ typedef struct {            /* DEVICE pointers; any may be NULL (sum, samples: s
 int atr_gather_radiance(atr_ctx* ctx, const float* points, const float* normals, int64_t npoints,
                         int32_t nsamples, uint32_t first_sample, int64_t point_base, int32_t bounce_limit,
                         uint64_t seed, const atr_gather_radiance_out* out, int32_t sort_bits, void* stream);
+
+/* Light probes (lighting for moving objects, or for any normal at all, from points in free space): the
+   radiance arriving at a point over the WHOLE sphere, projected on the nine real spherical harmonics
+   of bands 0..2 per colour channel. A probe has no normal and no surface. For npoints probes, nsamples
+   paths per probe are started on the device, each one cast_ray from the probe along a direction drawn
+   uniformly over the sphere; per probe 27 sums are kept in sample order. No ray array exists anywhere.
+   Every f32 operation below is separately rounded, in the order written.
+   Sample. Sample s of probe i:
+     state, stream = the path stream of (seed, pixel = point_base + i, sample = first_sample + s)
+                     (state = splitmix64(seed ^ pixel ^ sample << 40), increment 2 pixel + 1);
+     up to 32 tries, each: r0, r1, r2 = three rand_bi draws, in that order;
+                           l2 = (r0*r0 + r1*r1) + r2*r2;
+     the first try with 0x1p-10f <= l2 && l2 <= 1.0f is accepted: d = (r0, r1, r2) * (1 / sqrtf(l2));
+     if all 32 tries fail, d = (0, 0, 1).
+   Rejection inside a radial shell is uniform in direction and needs no sine or cosine, so the device
+   and plain C agree bit for bit (atr_probe_directions below is the same function on the host). A try
+   is accepted with probability about 0.5236; the fallback has a probability of about 1e-10 per sample
+   and exists so that the loop ends on every lane. The sample's colour is cast_ray(p, d, bounce_limit)
+   (renderer.cpp:213-262) continued on the same stream after those draws, exactly as in
+   atr_gather_radiance. Every sample of a valid probe is traced: there is no tangent plane and no
+   untraced state. The culled triangle test applies as everywhere: a probe inside a closed mesh sees
+   out through its back faces.
+   Basis, on d = (x, y, z), as f32 literals:
+     Y0 = 0.282094792f                 Y1 = 0.488602512f*y               Y2 = 0.488602512f*z
+     Y3 = 0.488602512f*x               Y4 = 1.092548431f*(x*y)           Y5 = 1.092548431f*(y*z)
+     Y6 = 0.315391565f*((3.0f*(z*z)) - 1.0f)                             Y7 = 1.092548431f*(x*z)
+     Y8 = 0.546274215f*((x*x) - (y*y))
+   (atr_sh_basis below evaluates them on the host.)
+   Probe outputs. For each sample in sample order, sum[3k+c] = sum[3k+c] + (colour.c * Yk(d)); ray_casts
+   adds up cast_ray's bounce counts. Both start from 0 when first_sample == 0. When first_sample > 0,
+   sum is required: it is read as the starting value and written back, and ray_casts (if given) is read,
+   added to and written back. sh[3k+c] = (sum[3k+c] * 12.566370614f) / float(first_sample + nsamples):
+   the Monte-Carlo estimate of the radiance's projection on Yk, not clamped. sample_rgb and dirs are
+   per-call outputs, 3 floats per (probe, sample) of this call, probe-major: written whole, never read.
+   Invalid probes. A probe is invalid when p is not finite. It traces nothing: its invalid byte is 1,
+   its sample_rgb and dirs rows are zeros; with first_sample == 0 its sh, sum and ray_casts are written
+   0, with first_sample > 0 they are left as they are. Its neighbours are untouched; no NaN reaches the
+   traversal.
+   traced_rays accumulates every segment traced: one first segment per sample of a valid probe plus the
+   bounce rays.
+   Consequences (each is tested):
+     1. With bounce_limit == 1, ray_casts[i] equals the count of atr_trace_rays(p_i, dirs[i, s]) with
+        t < 3.402823466e38, and the sample_rgb of the misses is the sky's emission.
+     2. A batch cut at any probe, the second call's point_base advanced by the cut, gives the per-probe
+        outputs of one call; a sample range cut in two calls that continue through sum and ray_casts
+        gives the bits of one call, and the sample_rgb and dirs rows concatenate.
+     3. No output bit depends on sort_bits, on the tuning's path_batch_log2, or on the stream.
+   sort_bits: -1 = the tuning's path_sort_bits, 0 = queue order, 2..7 as for atr_radiance_rays. It
+   orders the bounce levels' queues only; the first segments are traced in (probe, sample) order.
+   Ranges, ATR_E_INVALID otherwise: npoints >= 0 and npoints * nsamples < 2^31; nsamples 1..65,536;
+   first_sample + nsamples <= 2^24; point_base >= 0 and point_base + npoints <= 2^32 (the queues carry
+   the stream index in 32 bits); bounce_limit 1..64; sort_bits as above. ATR_E_INVALID also for ctx
+   NULL; for out or points NULL with npoints > 0; for sum NULL with first_sample > 0; for all seven
+   pointers of out NULL with npoints > 0. ATR_E_NOSCENE before an upload. npoints == 0: ATR_OK, nothing
+   is enqueued or written.
+   points: DEVICE, 3 floats per probe. Asynchronous on `stream`; atr_render_wait covers it (tiles_done
+   0; a tree-depth flag surfaces as ATR_E_TREE_DEPTH), atr_last_kernel_ms times it. It runs on a path
+   workspace, in batches of whole probes of about the tuning's 2^path_batch_log2 paths (at least one
+   probe). There is no cell-kernel fallback: if no workspace can be had the call returns
+   -(1000 + hipErrorOutOfMemory) before anything is enqueued, every buffer untouched. No struct and no
+   ABI version change. */
+typedef struct {            /* DEVICE pointers; any may be NULL (sum: see above) */
+    float*    sh;           /* 27 per probe, index 3*k + c (coefficient k = 0..8, channel c): (sum * 12.566370614f) / float(first_sample + nsamples) */
+    float*    sum;          /* 27 per probe: running f32 sums, in sample order */
+    uint32_t* ray_casts;    /* per probe: cast_ray's bounce count summed over its samples */
+    uint8_t*  invalid;      /* per probe: 1 iff the point is not finite */
+    float*    sample_rgb;   /* 3 per (probe, sample) of THIS call, probe-major */
+    float*    dirs;         /* 3 per (probe, sample) of this call: the generated direction */
+    unsigned long long* traced_rays;   /* one accumulator */
+} atr_probe_sh_out;
+int atr_probe_sh(atr_ctx* ctx, const float* points, int64_t npoints, int32_t nsamples, uint32_t first_sample,
+                 int64_t point_base, int32_t bounce_limit, uint64_t seed, const atr_probe_sh_out* out,
+                 int32_t sort_bits, void* stream);
+/* The probes' sampler and basis on the host: no device, no context. atr_probe_directions writes the
+   direction of every (probe, sample) (3 floats, probe-major; the bits atr_probe_sh's dirs holds for a
+   valid probe) and the try that was accepted (1..32, or 33 for the fallback); either output may be
+   NULL. Its ranges are atr_probe_sh's. atr_sh_basis writes Y0..Y8 of n directions, 9 floats each. */
+int atr_probe_directions(int64_t npoints, int32_t nsamples, uint32_t first_sample, int64_t point_base,
+                         uint64_t seed, float* dirs_out, uint8_t* tries_out);
+int atr_sh_basis(const float* dirs, int64_t n, float* basis_out /* 9 per direction */);
 
 /* Lightmap texels: the surface points a lightmap baker feeds to the gathers above, one per texel of
    the mesh's UV layout, made on the device; atr_texels_to_image turns per-texel results back into an
