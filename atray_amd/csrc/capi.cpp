@@ -614,6 +614,23 @@ hipError_t record_stop(atr_ctx* c, hipStream_t s, hipEvent_t done) {
     return hipEventRecord(c->ev_stop, s);
 }
 
+// The opening and the closing of a device call on stream s: the start of its timed range, and its
+// completion record -- `done`, the traced-ray ring event that covers the call, or null for ev_stop,
+// which the stream's list then notes (note_launch) -- with what atr_render_wait reads of it.
+hipError_t call_begin(atr_ctx* c, hipStream_t s) {
+    c->prog_active = false;
+    return hipEventRecord(c->ev_start, s);
+}
+hipError_t call_end(atr_ctx* c, hipStream_t s, hipEvent_t done, int32_t ntiles = 0) {
+    hipError_t e = record_stop(c, s, done);
+    if (e == hipSuccess) e = note_launch(c, s, c->ev_last != c->ev_stop);  // a ring event covers it
+    if (e != hipSuccess) return e;
+    c->have_render = true;
+    c->last_stream = s;
+    c->last_ntiles = ntiles;
+    return hipSuccess;
+}
+
 int launch_planned(atr_ctx* c, BlockSet* bs, RenderParams& P, int sched, hipStream_t s) {
     const int32_t nb = int32_t(bs->host.size());
     // on top of a user cell plan too: its classes order the base list (and the multi-frame
@@ -1756,7 +1773,6 @@ int atr_render_start_ex(atr_ctx* c, const atr_camera* cam, const atr_tile* tiles
     int rc = ATR_OK;
     BlockSet* bs = get_blocks(c, tiles, ntiles, cam->width, cam->height, rc);
     if (!bs) return rc;
-    c->prog_active = false;
     RenderParams P;
     std::memset(&P, 0, sizeof(P));
     P.cam = *cam;
@@ -1774,8 +1790,9 @@ int atr_render_start_ex(atr_ctx* c, const atr_camera* cam, const atr_tile* tiles
     P.error_flag = c->d_error;
     P.counters = nullptr;
     apply_tuning(c, P);
-    HIPCHK(hipEventRecord(c->ev_start, s));
+    HIPCHK(call_begin(c, s));
     if ((rc = launch_planned(c, bs, P, wave, s))) return rc;
+    // not call_end: launch_planned records the completion itself, ahead of its plan kernels
     HIPCHK(note_launch(c, s, c->ev_last != c->ev_stop));  // a ring event covers it
     c->have_render = true;
     c->last_stream = s;
@@ -1808,7 +1825,6 @@ int atr_render_start_samples(atr_ctx* c, const atr_camera* cam, const atr_tile* 
     int rc = ATR_OK;
     BlockSet* bs = get_blocks(c, tiles, ntiles, cam->width, cam->height, rc);
     if (!bs) return rc;
-    c->prog_active = false;
     RenderParams P;
     std::memset(&P, 0, sizeof(P));
     P.cam = *cam;
@@ -1827,14 +1843,10 @@ int atr_render_start_samples(atr_ctx* c, const atr_camera* cam, const atr_tile* 
     P.first_sample = first_sample;
     P.sample_sum = sample_sum;
     apply_tuning(c, P);
-    HIPCHK(hipEventRecord(c->ev_start, s));
+    HIPCHK(call_begin(c, s));
     hipEvent_t done = nullptr;
     HIPCHK(launch_render(c, P, sched, s, &done));
-    HIPCHK(record_stop(c, s, done));
-    HIPCHK(note_launch(c, s, c->ev_last != c->ev_stop));  // a ring event covers it
-    c->have_render = true;
-    c->last_stream = s;
-    c->last_ntiles = ntiles;
+    HIPCHK(call_end(c, s, done, ntiles));
     return ATR_OK;
 } ATR_ABI_CATCH
 
@@ -1860,7 +1872,6 @@ int atr_render_start_adaptive(atr_ctx* c, const atr_camera* cam, const atr_tile*
     BlockSet* bs = get_blocks(c, tiles, ntiles, cam->width, cam->height, rc);
     if (!bs) return rc;
     if (!c->adapt_info) HIPCHK(hipMalloc(&c->adapt_info, atr_ctx::kAdaptSlots * 4 * sizeof(unsigned long long)));
-    c->prog_active = false;
     RenderParams P;
     std::memset(&P, 0, sizeof(P));
     P.cam = *cam;
@@ -1885,7 +1896,7 @@ int atr_render_start_adaptive(atr_ctx* c, const atr_camera* cam, const atr_tile*
     live.tolerance = tolerance;
     const int slot = c->adapt_next;
     live.info = c->adapt_info + 4 * slot;
-    HIPCHK(hipEventRecord(c->ev_start, s));
+    HIPCHK(call_begin(c, s));
     // the next slot of the ring, never the one atr_render_adaptive_info reads now: a call that
     // fails below (no workspace) has touched nothing the caller can see
     HIPCHK(hipMemsetAsync(live.info, 0, 4 * sizeof(unsigned long long), s));
@@ -1893,11 +1904,7 @@ int atr_render_start_adaptive(atr_ctx* c, const atr_camera* cam, const atr_tile*
     HIPCHK(launch_render(c, P, kSchedPaths, s, &done, &live));
     c->adapt_next = (slot + 1) % atr_ctx::kAdaptSlots;
     c->adapt_last = slot;
-    HIPCHK(record_stop(c, s, done));
-    HIPCHK(note_launch(c, s, c->ev_last != c->ev_stop));  // a ring event covers it
-    c->have_render = true;
-    c->last_stream = s;
-    c->last_ntiles = ntiles;
+    HIPCHK(call_end(c, s, done, ntiles));
     return ATR_OK;
 } ATR_ABI_CATCH
 
@@ -1908,6 +1915,16 @@ int atr_render_start_adaptive(atr_ctx* c, const atr_camera* cam, const atr_tile*
 // counter and the ring's counters in a QueryParams and enqueues the query's own kernel.
 extern "C++" {  // a template
 namespace {
+// Argument domains the query calls share (atray.h). The stream hash shifts the sample index by 40
+// bits, and float(first_sample + nsamples) is exact up to 2^24; the path queues carry the stream
+// index, base + item, in 32 bits.
+bool sample_range_ok(int32_t nsamples, uint32_t first_sample) {
+    return nsamples >= 1 && nsamples <= 65536 && uint64_t(first_sample) + uint64_t(nsamples) <= (uint64_t(1) << 24);
+}
+bool stream_base_ok(int64_t base, int64_t n) { return base >= 0 && base <= (int64_t(1) << 32) - n; }
+bool sort_bits_ok(int32_t bits) { return bits == -1 || bits == 0 || (bits >= 2 && bits <= kMaxSortBits); }
+bool bounce_limit_ok(int32_t bl) { return bl >= 1 && bl <= kMaxPathBounces; }
+
 // The argument checks both queries share (atray.h); `out` is the required output.
 int query_args(atr_ctx* c, const float* origins, const float* directions, int64_t nrays, const void* out,
                int32_t variant, int32_t sort_bits) {
@@ -1915,7 +1932,7 @@ int query_args(atr_ctx* c, const float* origins, const float* directions, int64_
     if (nrays < 0 || nrays >= (int64_t(1) << 31)) return ATR_E_INVALID;
     if (nrays > 0 && (!out || !origins || !directions)) return ATR_E_INVALID;
     if (variant != ATR_KERNEL_AUTO && variant != ATR_KERNEL_FLAT && variant != ATR_KERNEL_LANE) return ATR_E_INVALID;
-    if (sort_bits != -1 && sort_bits != 0 && (sort_bits < 2 || sort_bits > kMaxSortBits)) return ATR_E_INVALID;
+    if (!sort_bits_ok(sort_bits)) return ATR_E_INVALID;
     if (!c->d_scene) return ATR_E_NOSCENE;
     return ATR_OK;
 }
@@ -1966,8 +1983,7 @@ int query_call(atr_ctx* c, const float* origins, const float* directions, int64_
         so.start = so.hist + ws.nbins;
         so.part = so.start + ws.nbins;
     }
-    c->prog_active = false;
-    HIPCHK(hipEventRecord(c->ev_start, s));
+    HIPCHK(call_begin(c, s));
     ws.used = true;  // from here on kernels of this call may be in flight on s
     ws.stream = s;
     hipEvent_t done = nullptr;
@@ -1982,11 +1998,86 @@ int query_call(atr_ctx* c, const float* origins, const float* directions, int64_
         done = c->tev[k];
     }
     HIPCHK(hipEventRecord(ws.ev, s));
-    HIPCHK(record_stop(c, s, done));
-    HIPCHK(note_launch(c, s, c->ev_last != c->ev_stop));  // a ring event covers it
-    c->have_render = true;
-    c->last_stream = s;
-    c->last_ntiles = 0;
+    HIPCHK(call_end(c, s, done));
+    return ATR_OK;
+}
+
+// The fields a path query's params share with the engine's launch (RadianceParams,
+// GatherRadianceParams and ProbeShParams name them alike), from a bound PathParams.
+template <class Params>
+void bind_path_query(const PathParams& Q, uint32_t first_sample, Params& R) {
+    R.scene = Q.scene;
+    R.nsamples = Q.cam.samples_per_pixel;
+    R.first_sample = first_sample;
+    R.bounce_limit = Q.cam.bounce_limit;
+    R.hyb_a = Q.hyb_a;
+    R.hyb_b = Q.hyb_b;
+    R.seed = Q.seed;
+    R.q0 = Q.q[0];
+    R.cap = Q.cap;
+    R.out = Q.out;
+    R.ctl = Q.ctl;
+    R.sort = Q.sort;
+    R.error_flag = Q.error_flag;
+}
+
+// The path engine on a caller's items (atray.h): atr_radiance_rays, atr_gather_radiance
+// and atr_probe_sh. The call is `units` units of per_unit paths each (groups of 64 rays, points,
+// probes), batched the way launch_paths_range batches over cells: a batch is a whole number of units,
+// at least one even when per_unit exceeds the tuned batch size, so a unit's paths never straddle two
+// batches. Per batch, `set_batch(first unit, units)` sets the range in the call's params R, then the
+// batch's reset, `entry`, the engine's own bounce levels and `resolve`. The workspace is obtained
+// before anything is enqueued and there is no cell-kernel fallback: the tuned batch size is tried even
+// below 2^16 paths, as for an adaptive pass. The traced rays go through a set of the ring, as a
+// render's and a query's do.
+template <class Params, class SetBatch>
+int path_query_call(atr_ctx* c, void* stream, int32_t sort_bits, int32_t bounce_limit, int32_t nsamples,
+                    uint32_t first_sample, uint64_t seed, unsigned long long* traced_out, int64_t units,
+                    int64_t per_unit, Params& R, SetBatch set_batch,
+                    hipError_t (*entry)(const Params&, int, hipStream_t),
+                    hipError_t (*resolve)(const Params&, hipStream_t)) {
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // the order is of the bounce levels' queues: without a second level there is nothing to order
+    int32_t bits = clamp_sort_bits(bounce_limit >= 2 ? (sort_bits < 0 ? c->tune.path_sort_bits : sort_bits) : 0);
+    atr_ctx::PathWS* ws = nullptr;
+    int64_t per_batch = 0;  // units
+    HIPCHK(path_batches(c, s, per_unit, units, bounce_limit, std::min(16, c->tune.path_batch_log2), false, bits, ws,
+                        per_batch));
+    PathParams Q;
+    std::memset(&Q, 0, sizeof(Q));
+    Q.cam.bounce_limit = bounce_limit;
+    Q.cam.samples_per_pixel = uint32_t(nsamples);
+    Q.scene = c->d_scene;
+    Q.seed = seed;
+    Q.error_flag = c->d_error;
+    Q.hyb_a = c->tune.hybrid_a;
+    Q.hyb_b = c->tune.hybrid_b;
+    bind_path_workspace(c, ws, bits, Q);
+    bind_path_query(Q, first_sample, R);
+    HIPCHK(call_begin(c, s));
+    hipEvent_t done = nullptr;
+    int k = -1;
+    if (traced_out) {
+        HIPCHK(ring_take(c, s, k, Q.traced_rays));
+        R.traced_rays = Q.traced_rays;
+    }
+    for (int64_t u0 = 0; u0 < units; u0 += per_batch) {
+        const int64_t nu = std::min<int64_t>(per_batch, units - u0);
+        Q.ncells = int32_t(nu);
+        set_batch(u0, nu);
+        HIPCHK(reset_path_batch(Q, bounce_limit, bits, s));
+        HIPCHK(entry(R, c->ncu, s));
+        HIPCHK(launch_bounce_levels(c, Q, bounce_limit, bits, s));
+        HIPCHK(resolve(R, s));
+    }
+    if (k >= 0) {
+        HIPCHK(atr_launch_traced_finish(Q.traced_rays, traced_out, s));
+        HIPCHK(ring_done(c, s, k));
+        done = c->tev[k];
+    }
+    HIPCHK(hipEventRecord(ws->ev, s));
+    HIPCHK(call_end(c, s, done));
     return ATR_OK;
 }
 }  // namespace
@@ -2040,8 +2131,7 @@ int atr_gather_occlusion(atr_ctx* c, const float* points, const float* normals, 
                          int32_t nsamples, uint32_t first_sample, int64_t point_base, uint64_t seed,
                          const atr_gather_out* out, int32_t variant, void* stream) try {
     if (!c) return ATR_E_INVALID;
-    if (npoints < 0 || nsamples < 1 || nsamples > 65536) return ATR_E_INVALID;
-    if (uint64_t(first_sample) + uint64_t(nsamples) > (uint64_t(1) << 24)) return ATR_E_INVALID;
+    if (npoints < 0 || !sample_range_ok(nsamples, first_sample)) return ATR_E_INVALID;
     if (point_base < 0 || npoints > (int64_t(1) << 39) || point_base > (int64_t(1) << 39) - npoints) return ATR_E_INVALID;
     if (npoints >= (int64_t(1) << 31) || npoints * int64_t(nsamples) >= (int64_t(1) << 31)) return ATR_E_INVALID;
     if (npoints > 0 && (!out || !points || !normals)) return ATR_E_INVALID;
@@ -2083,8 +2173,7 @@ int atr_gather_occlusion(atr_ctx* c, const float* points, const float* normals, 
 // library's -ffp-contract=off. No device, no context.
 int atr_gather_directions(const float* normals, int64_t npoints, int32_t nsamples, uint32_t first_sample,
                           int64_t point_base, uint64_t seed, float* dirs_out, uint8_t* traced_out) try {
-    if (npoints < 0 || nsamples < 1 || nsamples > 65536) return ATR_E_INVALID;
-    if (uint64_t(first_sample) + uint64_t(nsamples) > (uint64_t(1) << 24)) return ATR_E_INVALID;
+    if (npoints < 0 || !sample_range_ok(nsamples, first_sample)) return ATR_E_INVALID;
     if (point_base < 0 || npoints > (int64_t(1) << 39) || point_base > (int64_t(1) << 39) - npoints) return ATR_E_INVALID;
     if (npoints >= (int64_t(1) << 31) || npoints * int64_t(nsamples) >= (int64_t(1) << 31)) return ATR_E_INVALID;
     if (npoints > 0 && !normals) return ATR_E_INVALID;
@@ -2111,120 +2200,51 @@ int atr_gather_directions(const float* normals, int64_t npoints, int32_t nsample
     return ATR_OK;
 } ATR_ABI_CATCH
 
-// Path-traced radiance along the caller's rays (atray.h): the path engine on a path
-// workspace, batched over groups of 64 rays the way launch_paths_range batches over cells, with the
-// entry kernel and the per-ray resolve of radiance.hip around the engine's own bounce levels. The
-// workspace is obtained before anything is enqueued and there is no cell-kernel fallback: the tuned
-// batch size is tried even below 2^16 paths, as for an adaptive pass. The traced rays go through a
-// set of the ring, as a render's and a query's do.
+// Path-traced radiance along the caller's rays (atray.h): path_query_call over groups of
+// 64 rays, the last of which may be short, with the entry kernel and the per-ray resolve of
+// radiance.hip.
 int atr_radiance_rays(atr_ctx* c, const float* origins, const float* directions, int64_t nrays, int32_t nsamples,
                       uint32_t first_sample, int64_t ray_base, int32_t bounce_limit, uint64_t seed,
                       const atr_radiance_out* out, int32_t sort_bits, void* stream) try {
     if (!c) return ATR_E_INVALID;
-    if (nrays < 0 || nrays >= (int64_t(1) << 31) || nsamples < 1 || nsamples > 65536) return ATR_E_INVALID;
-    // the stream hash shifts the sample index by 40 bits, and float(total) is exact up to 2^24
-    if (uint64_t(first_sample) + uint64_t(nsamples) > (uint64_t(1) << 24)) return ATR_E_INVALID;
-    // the queues carry the stream index in 32 bits
-    if (ray_base < 0 || ray_base > (int64_t(1) << 32) - nrays) return ATR_E_INVALID;
-    if (bounce_limit < 1 || bounce_limit > kMaxPathBounces) return ATR_E_INVALID;
-    if (sort_bits != -1 && sort_bits != 0 && (sort_bits < 2 || sort_bits > kMaxSortBits)) return ATR_E_INVALID;
+    if (nrays < 0 || nrays >= (int64_t(1) << 31) || !sample_range_ok(nsamples, first_sample)) return ATR_E_INVALID;
+    if (!stream_base_ok(ray_base, nrays) || !bounce_limit_ok(bounce_limit) || !sort_bits_ok(sort_bits))
+        return ATR_E_INVALID;
     if (nrays > 0 && (!out || !origins || !directions)) return ATR_E_INVALID;
     if (out && first_sample > 0 && !out->sum) return ATR_E_INVALID;
     if (nrays > 0 && !out->rgb && !out->sum && !out->ray_casts && !out->invalid && !out->traced_rays)
         return ATR_E_INVALID;
     if (!c->d_scene) return ATR_E_NOSCENE;
     if (nrays == 0) return ATR_OK;
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int64_t per_group = 64 * int64_t(nsamples), groups = (nrays + 63) / 64;
-    // the order is of the bounce levels' queues: without a second level there is nothing to order
-    int32_t bits = clamp_sort_bits(bounce_limit >= 2 ? (sort_bits < 0 ? c->tune.path_sort_bits : sort_bits) : 0);
-    atr_ctx::PathWS* ws = nullptr;
-    int64_t cells = 0;
-    HIPCHK(path_batches(c, s, per_group, groups, bounce_limit, std::min(16, c->tune.path_batch_log2), false, bits, ws,
-                        cells));
-    PathParams Q;
-    std::memset(&Q, 0, sizeof(Q));
-    Q.cam.bounce_limit = bounce_limit;
-    Q.cam.samples_per_pixel = uint32_t(nsamples);
-    Q.scene = c->d_scene;
-    Q.seed = seed;
-    Q.error_flag = c->d_error;
-    Q.hyb_a = c->tune.hybrid_a;
-    Q.hyb_b = c->tune.hybrid_b;
-    bind_path_workspace(c, ws, bits, Q);
     RadianceParams R;
     std::memset(&R, 0, sizeof(R));
-    R.scene = Q.scene;
     R.o = origins;
     R.d = directions;
-    R.nsamples = uint32_t(nsamples);
-    R.first_sample = first_sample;
-    R.bounce_limit = bounce_limit;
-    R.hyb_a = Q.hyb_a;
-    R.hyb_b = Q.hyb_b;
     R.ray_base = ray_base;
-    R.seed = seed;
-    R.q0 = Q.q[0];
-    R.cap = Q.cap;
-    R.out = Q.out;
-    R.ctl = Q.ctl;
-    R.sort = Q.sort;
-    R.error_flag = Q.error_flag;
     R.rgb = out->rgb;
     R.sum = out->sum;
     R.ray_casts = out->ray_casts;
     R.invalid = out->invalid;
-    c->prog_active = false;
-    HIPCHK(hipEventRecord(c->ev_start, s));
-    hipEvent_t done = nullptr;
-    int k = -1;
-    if (out->traced_rays) {
-        HIPCHK(ring_take(c, s, k, Q.traced_rays));
-        R.traced_rays = Q.traced_rays;
-    }
-    for (int64_t g0 = 0; g0 < groups; g0 += cells) {  // no batch crosses a group
-        const int64_t r0 = g0 * 64;
-        Q.ncells = int32_t(std::min<int64_t>(cells, groups - g0));
-        R.ray0 = uint32_t(r0);
-        R.n = uint32_t(std::min<int64_t>(int64_t(Q.ncells) * 64, nrays - r0));
-        HIPCHK(reset_path_batch(Q, bounce_limit, bits, s));
-        HIPCHK(atr_launch_radiance_entry(R, c->ncu, s));
-        HIPCHK(launch_bounce_levels(c, Q, bounce_limit, bits, s));
-        HIPCHK(atr_launch_radiance_resolve(R, s));
-    }
-    if (k >= 0) {
-        HIPCHK(atr_launch_traced_finish(Q.traced_rays, out->traced_rays, s));
-        HIPCHK(ring_done(c, s, k));
-        done = c->tev[k];
-    }
-    HIPCHK(hipEventRecord(ws->ev, s));
-    HIPCHK(record_stop(c, s, done));
-    HIPCHK(note_launch(c, s, c->ev_last != c->ev_stop));  // a ring event covers it
-    c->have_render = true;
-    c->last_stream = s;
-    c->last_ntiles = 0;
-    return ATR_OK;
+    return path_query_call(c, stream, sort_bits, bounce_limit, nsamples, first_sample, seed, out->traced_rays,
+                           (nrays + 63) / 64, 64 * int64_t(nsamples), R,
+                           [&](int64_t g0, int64_t ng) {  // no batch crosses a group
+                               R.ray0 = uint32_t(g0 * 64);
+                               R.n = uint32_t(std::min<int64_t>(ng * 64, nrays - g0 * 64));
+                           },
+                           atr_launch_radiance_entry, atr_launch_radiance_resolve);
 } ATR_ABI_CATCH
 
-// Hemisphere radiance gathered on the device (atray.h): atr_radiance_rays' flow with the
-// point as the unit of batching -- a batch is a whole number of points (at least one, even when
-// nsamples exceeds the tuned batch size), so a point's samples never straddle two batches and the
-// resolve sums them in sample order in one launch. The entry kernel and the per-point resolve of
-// gather_radiance.hip around the engine's own bounce levels; the workspace is obtained before anything
-// is enqueued and there is no cell-kernel fallback.
+// Hemisphere radiance gathered on the device (atray.h): path_query_call over points, so
+// a point's samples never straddle two batches and the resolve sums them in sample order in one
+// launch, with the entry kernel and the per-point resolve of gather_radiance.hip.
 int atr_gather_radiance(atr_ctx* c, const float* points, const float* normals, int64_t npoints, int32_t nsamples,
                         uint32_t first_sample, int64_t point_base, int32_t bounce_limit, uint64_t seed,
                         const atr_gather_radiance_out* out, int32_t sort_bits, void* stream) try {
     if (!c) return ATR_E_INVALID;
-    if (npoints < 0 || npoints >= (int64_t(1) << 31) || nsamples < 1 || nsamples > 65536) return ATR_E_INVALID;
+    if (npoints < 0 || npoints >= (int64_t(1) << 31) || !sample_range_ok(nsamples, first_sample)) return ATR_E_INVALID;
     if (npoints * int64_t(nsamples) >= (int64_t(1) << 31)) return ATR_E_INVALID;
-    // the stream hash shifts the sample index by 40 bits, and float(samples) is exact up to 2^24
-    if (uint64_t(first_sample) + uint64_t(nsamples) > (uint64_t(1) << 24)) return ATR_E_INVALID;
-    // the queues carry the stream index in 32 bits
-    if (point_base < 0 || point_base > (int64_t(1) << 32) - npoints) return ATR_E_INVALID;
-    if (bounce_limit < 1 || bounce_limit > kMaxPathBounces) return ATR_E_INVALID;
-    if (sort_bits != -1 && sort_bits != 0 && (sort_bits < 2 || sort_bits > kMaxSortBits)) return ATR_E_INVALID;
+    if (!stream_base_ok(point_base, npoints) || !bounce_limit_ok(bounce_limit) || !sort_bits_ok(sort_bits))
+        return ATR_E_INVALID;
     if (npoints > 0 && (!out || !points || !normals)) return ATR_E_INVALID;
     if (out && first_sample > 0 && (!out->sum || !out->samples)) return ATR_E_INVALID;
     if (npoints > 0 && !out->rgb && !out->sum && !out->samples && !out->ray_casts && !out->invalid &&
@@ -2232,42 +2252,11 @@ int atr_gather_radiance(atr_ctx* c, const float* points, const float* normals, i
         return ATR_E_INVALID;
     if (!c->d_scene) return ATR_E_NOSCENE;
     if (npoints == 0) return ATR_OK;
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    // the order is of the bounce levels' queues: without a second level there is nothing to order
-    int32_t bits = clamp_sort_bits(bounce_limit >= 2 ? (sort_bits < 0 ? c->tune.path_sort_bits : sort_bits) : 0);
-    atr_ctx::PathWS* ws = nullptr;
-    int64_t per_batch = 0;  // points
-    HIPCHK(path_batches(c, s, nsamples, npoints, bounce_limit, std::min(16, c->tune.path_batch_log2), false, bits, ws,
-                        per_batch));
-    PathParams Q;
-    std::memset(&Q, 0, sizeof(Q));
-    Q.cam.bounce_limit = bounce_limit;
-    Q.cam.samples_per_pixel = uint32_t(nsamples);
-    Q.scene = c->d_scene;
-    Q.seed = seed;
-    Q.error_flag = c->d_error;
-    Q.hyb_a = c->tune.hybrid_a;
-    Q.hyb_b = c->tune.hybrid_b;
-    bind_path_workspace(c, ws, bits, Q);
     GatherRadianceParams R;
     std::memset(&R, 0, sizeof(R));
-    R.scene = Q.scene;
     R.p = points;
     R.nrm = normals;
-    R.nsamples = uint32_t(nsamples);
-    R.first_sample = first_sample;
-    R.bounce_limit = bounce_limit;
-    R.hyb_a = Q.hyb_a;
-    R.hyb_b = Q.hyb_b;
     R.point_base = point_base;
-    R.seed = seed;
-    R.q0 = Q.q[0];
-    R.cap = Q.cap;
-    R.out = Q.out;
-    R.ctl = Q.ctl;
-    R.sort = Q.sort;
-    R.error_flag = Q.error_flag;
     R.rgb = out->rgb;
     R.sum = out->sum;
     R.samples = out->samples;
@@ -2275,55 +2264,26 @@ int atr_gather_radiance(atr_ctx* c, const float* points, const float* normals, i
     R.invalid = out->invalid;
     R.sample_rgb = out->sample_rgb;
     R.dirs = out->dirs;
-    c->prog_active = false;
-    HIPCHK(hipEventRecord(c->ev_start, s));
-    hipEvent_t done = nullptr;
-    int k = -1;
-    if (out->traced_rays) {
-        HIPCHK(ring_take(c, s, k, Q.traced_rays));
-        R.traced_rays = Q.traced_rays;
-    }
-    for (int64_t p0 = 0; p0 < npoints; p0 += per_batch) {  // whole points
-        const int64_t np = std::min<int64_t>(per_batch, npoints - p0);
-        Q.ncells = int32_t(np);
-        R.point0 = uint32_t(p0);
-        R.npoints = uint32_t(np);
-        R.n = uint32_t(np * int64_t(nsamples));
-        HIPCHK(reset_path_batch(Q, bounce_limit, bits, s));
-        HIPCHK(atr_launch_gather_radiance_entry(R, c->ncu, s));
-        HIPCHK(launch_bounce_levels(c, Q, bounce_limit, bits, s));
-        HIPCHK(atr_launch_gather_radiance_resolve(R, s));
-    }
-    if (k >= 0) {
-        HIPCHK(atr_launch_traced_finish(Q.traced_rays, out->traced_rays, s));
-        HIPCHK(ring_done(c, s, k));
-        done = c->tev[k];
-    }
-    HIPCHK(hipEventRecord(ws->ev, s));
-    HIPCHK(record_stop(c, s, done));
-    HIPCHK(note_launch(c, s, c->ev_last != c->ev_stop));  // a ring event covers it
-    c->have_render = true;
-    c->last_stream = s;
-    c->last_ntiles = 0;
-    return ATR_OK;
+    return path_query_call(c, stream, sort_bits, bounce_limit, nsamples, first_sample, seed, out->traced_rays,
+                           npoints, nsamples, R,
+                           [&](int64_t p0, int64_t np) {  // whole points
+                               R.point0 = uint32_t(p0);
+                               R.npoints = uint32_t(np);
+                               R.n = uint32_t(np * int64_t(nsamples));
+                           },
+                           atr_launch_gather_radiance_entry, atr_launch_gather_radiance_resolve);
 } ATR_ABI_CATCH
 
-// Light probes as L2 spherical harmonics (atray.h): atr_gather_radiance's flow on points
-// without normals -- batches of whole probes, the entry kernel and the per-probe resolve of
-// probe_sh.hip around the engine's own bounce levels; the workspace is obtained before anything is
-// enqueued and there is no cell-kernel fallback.
+// Light probes as L2 spherical harmonics (atray.h): path_query_call over probes, points
+// without normals, with the entry kernel and the per-probe resolve of probe_sh.hip.
 int atr_probe_sh(atr_ctx* c, const float* points, int64_t npoints, int32_t nsamples, uint32_t first_sample,
                  int64_t point_base, int32_t bounce_limit, uint64_t seed, const atr_probe_sh_out* out,
                  int32_t sort_bits, void* stream) try {
     if (!c) return ATR_E_INVALID;
-    if (npoints < 0 || npoints >= (int64_t(1) << 31) || nsamples < 1 || nsamples > 65536) return ATR_E_INVALID;
+    if (npoints < 0 || npoints >= (int64_t(1) << 31) || !sample_range_ok(nsamples, first_sample)) return ATR_E_INVALID;
     if (npoints * int64_t(nsamples) >= (int64_t(1) << 31)) return ATR_E_INVALID;
-    // the stream hash shifts the sample index by 40 bits, and float(first_sample + nsamples) is exact up to 2^24
-    if (uint64_t(first_sample) + uint64_t(nsamples) > (uint64_t(1) << 24)) return ATR_E_INVALID;
-    // the queues carry the stream index in 32 bits
-    if (point_base < 0 || point_base > (int64_t(1) << 32) - npoints) return ATR_E_INVALID;
-    if (bounce_limit < 1 || bounce_limit > kMaxPathBounces) return ATR_E_INVALID;
-    if (sort_bits != -1 && sort_bits != 0 && (sort_bits < 2 || sort_bits > kMaxSortBits)) return ATR_E_INVALID;
+    if (!stream_base_ok(point_base, npoints) || !bounce_limit_ok(bounce_limit) || !sort_bits_ok(sort_bits))
+        return ATR_E_INVALID;
     if (npoints > 0 && (!out || !points)) return ATR_E_INVALID;
     if (out && first_sample > 0 && !out->sum) return ATR_E_INVALID;
     if (npoints > 0 && !out->sh && !out->sum && !out->ray_casts && !out->invalid && !out->sample_rgb && !out->dirs &&
@@ -2331,88 +2291,33 @@ int atr_probe_sh(atr_ctx* c, const float* points, int64_t npoints, int32_t nsamp
         return ATR_E_INVALID;
     if (!c->d_scene) return ATR_E_NOSCENE;
     if (npoints == 0) return ATR_OK;
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    // the order is of the bounce levels' queues: without a second level there is nothing to order
-    int32_t bits = clamp_sort_bits(bounce_limit >= 2 ? (sort_bits < 0 ? c->tune.path_sort_bits : sort_bits) : 0);
-    atr_ctx::PathWS* ws = nullptr;
-    int64_t per_batch = 0;  // probes
-    HIPCHK(path_batches(c, s, nsamples, npoints, bounce_limit, std::min(16, c->tune.path_batch_log2), false, bits, ws,
-                        per_batch));
-    PathParams Q;
-    std::memset(&Q, 0, sizeof(Q));
-    Q.cam.bounce_limit = bounce_limit;
-    Q.cam.samples_per_pixel = uint32_t(nsamples);
-    Q.scene = c->d_scene;
-    Q.seed = seed;
-    Q.error_flag = c->d_error;
-    Q.hyb_a = c->tune.hybrid_a;
-    Q.hyb_b = c->tune.hybrid_b;
-    bind_path_workspace(c, ws, bits, Q);
     ProbeShParams R;
     std::memset(&R, 0, sizeof(R));
-    R.scene = Q.scene;
     R.p = points;
-    R.nsamples = uint32_t(nsamples);
-    R.first_sample = first_sample;
-    R.bounce_limit = bounce_limit;
-    R.hyb_a = Q.hyb_a;
-    R.hyb_b = Q.hyb_b;
     R.point_base = point_base;
-    R.seed = seed;
-    R.q0 = Q.q[0];
-    R.cap = Q.cap;
-    R.out = Q.out;
-    R.ctl = Q.ctl;
-    R.sort = Q.sort;
-    R.error_flag = Q.error_flag;
     R.sh = out->sh;
     R.sum = out->sum;
     R.ray_casts = out->ray_casts;
     R.invalid = out->invalid;
     R.sample_rgb = out->sample_rgb;
     R.dirs = out->dirs;
-    c->prog_active = false;
-    HIPCHK(hipEventRecord(c->ev_start, s));
-    hipEvent_t done = nullptr;
-    int k = -1;
-    if (out->traced_rays) {
-        HIPCHK(ring_take(c, s, k, Q.traced_rays));
-        R.traced_rays = Q.traced_rays;
-    }
-    for (int64_t p0 = 0; p0 < npoints; p0 += per_batch) {  // whole probes
-        const int64_t np = std::min<int64_t>(per_batch, npoints - p0);
-        Q.ncells = int32_t(np);
-        R.point0 = uint32_t(p0);
-        R.npoints = uint32_t(np);
-        R.n = uint32_t(np * int64_t(nsamples));
-        HIPCHK(reset_path_batch(Q, bounce_limit, bits, s));
-        HIPCHK(atr_launch_probe_sh_entry(R, c->ncu, s));
-        HIPCHK(launch_bounce_levels(c, Q, bounce_limit, bits, s));
-        HIPCHK(atr_launch_probe_sh_resolve(R, s));
-    }
-    if (k >= 0) {
-        HIPCHK(atr_launch_traced_finish(Q.traced_rays, out->traced_rays, s));
-        HIPCHK(ring_done(c, s, k));
-        done = c->tev[k];
-    }
-    HIPCHK(hipEventRecord(ws->ev, s));
-    HIPCHK(record_stop(c, s, done));
-    HIPCHK(note_launch(c, s, c->ev_last != c->ev_stop));  // a ring event covers it
-    c->have_render = true;
-    c->last_stream = s;
-    c->last_ntiles = 0;
-    return ATR_OK;
+    return path_query_call(c, stream, sort_bits, bounce_limit, nsamples, first_sample, seed, out->traced_rays,
+                           npoints, nsamples, R,
+                           [&](int64_t p0, int64_t np) {  // whole probes
+                               R.point0 = uint32_t(p0);
+                               R.npoints = uint32_t(np);
+                               R.n = uint32_t(np * int64_t(nsamples));
+                           },
+                           atr_launch_probe_sh_entry, atr_launch_probe_sh_resolve);
 } ATR_ABI_CATCH
 
 // The probes' sampler and basis on the host (atray.h): the kernels' own functions (engine.h), compiled
 // with the library's -ffp-contract=off. No device, no context.
 int atr_probe_directions(int64_t npoints, int32_t nsamples, uint32_t first_sample, int64_t point_base, uint64_t seed,
                          float* dirs_out, uint8_t* tries_out) try {
-    if (npoints < 0 || npoints >= (int64_t(1) << 31) || nsamples < 1 || nsamples > 65536) return ATR_E_INVALID;
+    if (npoints < 0 || npoints >= (int64_t(1) << 31) || !sample_range_ok(nsamples, first_sample)) return ATR_E_INVALID;
     if (npoints * int64_t(nsamples) >= (int64_t(1) << 31)) return ATR_E_INVALID;
-    if (uint64_t(first_sample) + uint64_t(nsamples) > (uint64_t(1) << 24)) return ATR_E_INVALID;
-    if (point_base < 0 || point_base > (int64_t(1) << 32) - npoints) return ATR_E_INVALID;
+    if (!stream_base_ok(point_base, npoints)) return ATR_E_INVALID;
     for (int64_t i = 0; i < npoints; ++i) {
         for (int32_t s = 0; s < nsamples; ++s) {
             const int64_t k = i * nsamples + s;
@@ -2478,7 +2383,6 @@ int start_frames(atr_ctx* c, const atr_camera* cams, int32_t ncams, const atr_ti
     if (nframes > 1 && frame_stride < per_frame) return ATR_E_INVALID;
     const int32_t nb = int32_t(bs->host.size());
     if (int64_t(nb) * nframes > (int64_t(1) << 30)) return ATR_E_INVALID;
-    c->prog_active = false;
     RenderParams P;
     std::memset(&P, 0, sizeof(P));
     P.cam = *cam;
@@ -2494,7 +2398,7 @@ int start_frames(atr_ctx* c, const atr_camera* cams, int32_t ncams, const atr_ti
     P.traced_rays = fr->traced_rays;
     P.error_flag = c->d_error;
     apply_tuning(c, P);
-    HIPCHK(hipEventRecord(c->ev_start, s));
+    HIPCHK(call_begin(c, s));
     if (nframes == 1) {  // one frame: the single-frame plan applies
         P.nblocks = nb;
         P.frame_stride = frame_stride;
@@ -2512,6 +2416,7 @@ int start_frames(atr_ctx* c, const atr_camera* cams, int32_t ncams, const atr_ti
         HIPCHK(launch_render(c, P, sched, s, &done));
         HIPCHK(record_stop(c, s, done));
     }
+    // not call_end: launch_planned records the completion itself, ahead of its plan kernels
     HIPCHK(note_launch(c, s, c->ev_last != c->ev_stop));  // a ring event covers it
     c->have_render = true;
     c->last_stream = s;
@@ -2913,6 +2818,7 @@ int atr_render_start_progressive(atr_ctx* c, const atr_camera* cam, const atr_ti
         HIPCHK(hipEventRecord(c->prog_ev[size_t(g)], s));
         c->prog_end[size_t(g)] = e;
     }
+    // not call_begin / call_end: a progressive render leaves prog_active set
     HIPCHK(record_stop(c, s, nullptr));
     HIPCHK(note_launch(c, s));
     c->have_render = true;
@@ -3070,8 +2976,7 @@ int atr_texels_to_image(atr_ctx* c, const float* values, const int32_t* texel, i
         if (need_image && (rc = ensure_buf(ws.image, need_image, false))) return rc;
     }
     if (ws.used && ws.stream != s) HIPCHK(hipStreamWaitEvent(s, ws.ev, 0));
-    c->prog_active = false;
-    HIPCHK(hipEventRecord(c->ev_start, s));
+    HIPCHK(call_begin(c, s));
     ws.used = true;  // from here on kernels of this call may be in flight on s
     ws.stream = s;
     // the passes alternate between the caller's image and the workspace's; the last one writes the caller's
@@ -3101,11 +3006,7 @@ int atr_texels_to_image(atr_ctx* c, const float* values, const int32_t* texel, i
         HIPCHK(atr_launch_texel_fill(P, s));
     }
     HIPCHK(hipEventRecord(ws.ev, s));
-    HIPCHK(record_stop(c, s, nullptr));
-    HIPCHK(note_launch(c, s));
-    c->have_render = true;
-    c->last_stream = s;
-    c->last_ntiles = 0;
+    HIPCHK(call_end(c, s, nullptr));
     return ATR_OK;
 } ATR_ABI_CATCH
 
@@ -3157,8 +3058,7 @@ int atr_denoise(atr_ctx* c, const float* color, const atr_denoise_guides* guides
         if (need_guides && (rc = ensure_buf(ws.guides, need_guides, false))) return rc;
     }
     if (ws.used && ws.stream != s) HIPCHK(hipStreamWaitEvent(s, ws.ev, 0));
-    c->prog_active = false;
-    HIPCHK(hipEventRecord(c->ev_start, s));
+    HIPCHK(call_begin(c, s));
     ws.used = true;  // from here on kernels of this call may be in flight on s
     ws.stream = s;
     float4_t* img[2] = {static_cast<float4_t*>(ws.color.p), static_cast<float4_t*>(ws.color.p) + npix};
@@ -3193,11 +3093,7 @@ int atr_denoise(atr_ctx* c, const float* color, const atr_denoise_guides* guides
         HIPCHK(atr_launch_denoise_pass(P, g.normal != nullptr, position_on, colour_on, s));
     }
     HIPCHK(hipEventRecord(ws.ev, s));
-    HIPCHK(record_stop(c, s, nullptr));
-    HIPCHK(note_launch(c, s));
-    c->have_render = true;
-    c->last_stream = s;
-    c->last_ntiles = 0;
+    HIPCHK(call_end(c, s, nullptr));
     return ATR_OK;
 } ATR_ABI_CATCH
 
@@ -3273,8 +3169,7 @@ int atr_denoise_variance(atr_ctx* c, const float* color, const float* variance, 
         if (need_guides && (rc = ensure_buf(ws.guides, need_guides, false))) return rc;
     }
     if (ws.used && ws.stream != s) HIPCHK(hipStreamWaitEvent(s, ws.ev, 0));
-    c->prog_active = false;
-    HIPCHK(hipEventRecord(c->ev_start, s));
+    HIPCHK(call_begin(c, s));
     ws.used = true;  // from here on kernels of this call may be in flight on s
     ws.stream = s;
     float4_t* img[2] = {static_cast<float4_t*>(ws.color.p), static_cast<float4_t*>(ws.color.p) + npix};
@@ -3333,11 +3228,7 @@ int atr_denoise_variance(atr_ctx* c, const float* color, const float* variance, 
         HIPCHK(atr_launch_denoise_variance_pass(P, g.normal != nullptr, position_on, luminance_on, s));
     }
     HIPCHK(hipEventRecord(ws.ev, s));
-    HIPCHK(record_stop(c, s, nullptr));
-    HIPCHK(note_launch(c, s));
-    c->have_render = true;
-    c->last_stream = s;
-    c->last_ntiles = 0;
+    HIPCHK(call_end(c, s, nullptr));
     return ATR_OK;
 } ATR_ABI_CATCH
 
@@ -3427,14 +3318,9 @@ int atr_accumulate(atr_ctx* c, const float* color, const atr_denoise_guides* gui
     P.framebuffer = framebuffer;
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = the null stream (HIP convention)
-    c->prog_active = false;
-    HIPCHK(hipEventRecord(c->ev_start, s));
+    HIPCHK(call_begin(c, s));
     HIPCHK(atr_launch_accumulate(P, s));
-    HIPCHK(record_stop(c, s, nullptr));
-    HIPCHK(note_launch(c, s));
-    c->have_render = true;
-    c->last_stream = s;
-    c->last_ntiles = 0;
+    HIPCHK(call_end(c, s, nullptr));
     return ATR_OK;
 } ATR_ABI_CATCH
 
@@ -3490,14 +3376,9 @@ int atr_camera_rays(atr_ctx* c, const atr_camera* cam, int64_t first_pixel, int6
     P.d = directions;
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = the null stream (HIP convention)
-    c->prog_active = false;
-    HIPCHK(hipEventRecord(c->ev_start, s));
+    HIPCHK(call_begin(c, s));
     HIPCHK(atr_launch_camera_rays(P, s));
-    HIPCHK(record_stop(c, s, nullptr));
-    HIPCHK(note_launch(c, s));
-    c->have_render = true;
-    c->last_stream = s;
-    c->last_ntiles = 0;
+    HIPCHK(call_end(c, s, nullptr));
     return ATR_OK;
 } ATR_ABI_CATCH
 
@@ -3535,14 +3416,9 @@ int atr_camera_guides(atr_ctx* c, const atr_camera* cam, const atr_tile* tiles, 
     P.depth = out->depth;
     P.material = out->material;
     P.error_flag = c->d_error;
-    c->prog_active = false;
-    HIPCHK(hipEventRecord(c->ev_start, s));
+    HIPCHK(call_begin(c, s));
     HIPCHK(atr_launch_camera_guides(P, s));
-    HIPCHK(record_stop(c, s, nullptr));
-    HIPCHK(note_launch(c, s));
-    c->have_render = true;
-    c->last_stream = s;
-    c->last_ntiles = 0;
+    HIPCHK(call_end(c, s, nullptr));
     return ATR_OK;
 } ATR_ABI_CATCH
 

@@ -789,6 +789,60 @@ class Engine:
                                               C.c_void_p(count_ptr) if count_ptr else None, float(tolerance)),
               "adaptive pass start")
 
+    def _xyz(self, **arrays):
+        """The check of a query's (n, 3) inputs, by name: float32 tensors on the engine's device,
+        contiguous and of one length. Returns (the device, n)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        for name, a in arrays.items():
+            if not isinstance(a, torch.Tensor) or a.dtype != torch.float32 or a.dim() != 2 or a.shape[1] != 3:
+                raise ValueError(f"{name}: an (n, 3) float32 tensor is required")
+            if a.device != dev:
+                raise ValueError(f"{name}: not on {dev}")
+            if not a.is_contiguous():
+                raise ValueError(f"{name}: not contiguous")
+        first, *rest = arrays
+        for name in rest:
+            if arrays[name].shape[0] != arrays[first].shape[0]:
+                raise ValueError(f"{first} and {name} differ in length")
+        return dev, int(arrays[first].shape[0])
+
+    def _path_outputs(self, table, struct, noun, dev, n, ns, want, first_sample, given, required, keywords=False):
+        """The outputs of a path query (radiance_rays, gather_radiance, probe_sh) of n `noun`: `want`
+        checked against the call's output table (name -> (torch dtype name, trailing shape; "s" = ns), in
+        the order of `struct`'s pointers), the earlier call's tensors in `given` checked and taken as
+        they are -- those named in `required` must be there when first_sample > 0 -- and the rest
+        allocated. `keywords`: the tensors came as keyword arguments, not in a `start` dict. Returns
+        ({name: tensor}, the traced-ray tensor, the call's out-struct)."""
+        import torch
+        bad = [k for k in want if k not in table]
+        if bad:
+            raise ValueError(f"unknown outputs {bad}")
+        if ns is not None and not 1 <= ns <= 65536:
+            raise ValueError("nsamples: 1..65536")
+
+        def shape(k):
+            return (n,) + tuple(ns if d == "s" else d for d in table[k][1])
+
+        bad = [k for k in given if k not in ("sum", "ray_casts") + tuple(required)]
+        if bad:
+            raise ValueError(f"start: unknown entries {bad}")
+        for k, a in given.items():
+            dt = table[k][0]
+            if (not isinstance(a, torch.Tensor) or a.dtype != getattr(torch, dt) or a.device != dev
+                    or not a.is_contiguous() or tuple(a.shape) != shape(k)):
+                name = k if keywords else f"start[{k!r}]"
+                raise ValueError(f"{name}: a contiguous {dt} tensor of {n} {noun} on {dev} is required")
+        if int(first_sample) > 0 and any(k not in given for k in required):
+            names = " and ".join(required)
+            raise ValueError(f"{names}: required when first_sample > 0" if keywords else
+                             f"start: {names} {'are' if len(required) > 1 else 'is'} required when first_sample > 0")
+        out = {}
+        for k in tuple(want) + tuple(k for k in given if k not in want):
+            out[k] = given[k] if k in given else torch.empty(shape(k), dtype=getattr(torch, table[k][0]), device=dev)
+        traced = torch.zeros(1, dtype=torch.int64, device=dev)
+        return out, traced, struct(*[out[k].data_ptr() if k in out and n else None for k in table], traced.data_ptr())
+
     # atr_ray_hits outputs: name -> (torch dtype name, elements per ray, fill before the call)
     _RAY_OUTPUTS = {"t": ("float32", 1), "face": ("int32", 1), "model": ("int32", 1), "uv": ("float32", 2),
                     "kind": ("int32", 1), "material": ("int32", 1), "normal": ("float32", 3)}
@@ -802,20 +856,10 @@ class Engine:
         as int32 bits, MISS = -1 -- and the traced-ray count as a one-element int64 tensor); valid
         once the stream has run, e.g. after wait()."""
         import torch
-        dev = torch.device("cuda", self.device)
-        for name, a in (("orig", orig), ("dirs", dirs)):
-            if not isinstance(a, torch.Tensor) or a.dtype != torch.float32 or a.dim() != 2 or a.shape[1] != 3:
-                raise ValueError(f"{name}: an (n, 3) float32 tensor is required")
-            if a.device != dev:
-                raise ValueError(f"{name}: not on {dev}")
-            if not a.is_contiguous():
-                raise ValueError(f"{name}: not contiguous")
-        if orig.shape[0] != dirs.shape[0]:
-            raise ValueError("orig and dirs differ in length")
+        dev, n = self._xyz(orig=orig, dirs=dirs)
         bad = [k for k in outputs if k not in self._RAY_OUTPUTS]
         if bad:
             raise ValueError(f"unknown outputs {bad}")
-        n = int(orig.shape[0])
         out = {}
         for k in outputs:
             dt, per = self._RAY_OUTPUTS[k]
@@ -837,17 +881,7 @@ class Engine:
         (every ray unbounded). Returns (a uint8 tensor of ATR_OCCL_* in input order, the traced-ray count
         as a one-element int64 tensor); valid once the stream has run, e.g. after wait()."""
         import torch
-        dev = torch.device("cuda", self.device)
-        for name, a in (("orig", orig), ("dirs", dirs)):
-            if not isinstance(a, torch.Tensor) or a.dtype != torch.float32 or a.dim() != 2 or a.shape[1] != 3:
-                raise ValueError(f"{name}: an (n, 3) float32 tensor is required")
-            if a.device != dev:
-                raise ValueError(f"{name}: not on {dev}")
-            if not a.is_contiguous():
-                raise ValueError(f"{name}: not contiguous")
-        if orig.shape[0] != dirs.shape[0]:
-            raise ValueError("orig and dirs differ in length")
-        n = int(orig.shape[0])
+        dev, n = self._xyz(orig=orig, dirs=dirs)
         if t_max is not None:
             if not isinstance(t_max, torch.Tensor) or t_max.dtype != torch.float32 or t_max.dim() != 1:
                 raise ValueError("t_max: an (n,) float32 tensor is required")
@@ -889,17 +923,8 @@ class Engine:
         dirs: (n, nsamples, 3) float32 -- and the traced-sample count as a one-element int64 tensor);
         valid once the stream has run, e.g. after wait()."""
         import torch
-        dev = torch.device("cuda", self.device)
-        for name, a in (("points", points), ("normals", normals)):
-            if not isinstance(a, torch.Tensor) or a.dtype != torch.float32 or a.dim() != 2 or a.shape[1] != 3:
-                raise ValueError(f"{name}: an (n, 3) float32 tensor is required")
-            if a.device != dev:
-                raise ValueError(f"{name}: not on {dev}")
-            if not a.is_contiguous():
-                raise ValueError(f"{name}: not contiguous")
-        if points.shape[0] != normals.shape[0]:
-            raise ValueError("points and normals differ in length")
-        n, ns = int(points.shape[0]), int(nsamples)
+        dev, n = self._xyz(points=points, normals=normals)
+        ns = int(nsamples)
         if t_max is not None:
             if not isinstance(t_max, torch.Tensor) or t_max.dtype != torch.float32 or t_max.dim() != 1:
                 raise ValueError("t_max: an (n,) float32 tensor is required")
@@ -941,9 +966,9 @@ class Engine:
         vis, occ = out["visible"], out["occluded"]
         return vis.to(torch.float32) / torch.clamp(vis + occ, min=1).to(torch.float32)
 
-    # atr_radiance_out outputs: name -> (torch dtype name, elements per ray)
-    _RADIANCE_OUTPUTS = {"rgb": ("float32", 3), "sum": ("float32", 3), "ray_casts": ("int32", 1),
-                         "invalid": ("uint8", 1)}
+    # atr_radiance_out outputs: name -> (torch dtype name, trailing shape)
+    _RADIANCE_OUTPUTS = {"rgb": ("float32", (3,)), "sum": ("float32", (3,)), "ray_casts": ("int32", ()),
+                         "invalid": ("uint8", ())}
 
     def radiance_rays(self, orig, dirs, nsamples, bounces, seed=0, first_sample=0, ray_base=0, sort_bits=-1,
                       stream=None, want=("rgb", "ray_casts", "invalid"), sum=None, ray_casts=None):
@@ -957,40 +982,10 @@ class Engine:
         (a raw HIP stream), or torch's current one. Returns ({name: tensor}, the traced-ray count as a
         one-element int64 tensor); valid once the stream has run, e.g. after wait()."""
         import torch
-        dev = torch.device("cuda", self.device)
-        for name, a in (("orig", orig), ("dirs", dirs)):
-            if not isinstance(a, torch.Tensor) or a.dtype != torch.float32 or a.dim() != 2 or a.shape[1] != 3:
-                raise ValueError(f"{name}: an (n, 3) float32 tensor is required")
-            if a.device != dev:
-                raise ValueError(f"{name}: not on {dev}")
-            if not a.is_contiguous():
-                raise ValueError(f"{name}: not contiguous")
-        if orig.shape[0] != dirs.shape[0]:
-            raise ValueError("orig and dirs differ in length")
-        bad = [k for k in want if k not in self._RADIANCE_OUTPUTS]
-        if bad:
-            raise ValueError(f"unknown outputs {bad}")
-        n = int(orig.shape[0])
-        given = {"sum": sum, "ray_casts": ray_casts}
-        for k, a in given.items():
-            if a is None:
-                continue
-            dt, per = self._RADIANCE_OUTPUTS[k]
-            if (not isinstance(a, torch.Tensor) or a.dtype != getattr(torch, dt) or a.device != dev
-                    or not a.is_contiguous() or tuple(a.shape) != ((n, per) if per > 1 else (n,))):
-                raise ValueError(f"{k}: a contiguous {dt} tensor of {n} rays on {dev} is required")
-        if int(first_sample) > 0 and sum is None:
-            raise ValueError("sum: required when first_sample > 0")
-        out = {}
-        for k in tuple(want) + tuple(k for k, a in given.items() if a is not None and k not in want):
-            dt, per = self._RADIANCE_OUTPUTS[k]
-            if given.get(k) is not None:
-                out[k] = given[k]
-            else:
-                out[k] = torch.empty((n, per) if per > 1 else (n,), dtype=getattr(torch, dt), device=dev)
-        traced = torch.zeros(1, dtype=torch.int64, device=dev)
-        ro = atr_radiance_out(*[out[k].data_ptr() if k in out and n else None
-                                for k in ("rgb", "sum", "ray_casts", "invalid")], traced.data_ptr())
+        dev, n = self._xyz(orig=orig, dirs=dirs)
+        given = {k: a for k, a in (("sum", sum), ("ray_casts", ray_casts)) if a is not None}
+        out, traced, ro = self._path_outputs(self._RADIANCE_OUTPUTS, atr_radiance_out, "rays", dev, n, None, want,
+                                             first_sample, given, ("sum",), keywords=True)
         if stream is None:
             stream = torch.cuda.current_stream(dev).cuda_stream
         check(lib().atr_radiance_rays(self.h, C.c_void_p(orig.data_ptr()) if n else None,
@@ -1020,45 +1015,10 @@ class Engine:
         tensor}, the traced-ray count as a one-element int64 tensor); valid once the stream has run,
         e.g. after wait()."""
         import torch
-        dev = torch.device("cuda", self.device)
-        for name, a in (("points", points), ("normals", normals)):
-            if not isinstance(a, torch.Tensor) or a.dtype != torch.float32 or a.dim() != 2 or a.shape[1] != 3:
-                raise ValueError(f"{name}: an (n, 3) float32 tensor is required")
-            if a.device != dev:
-                raise ValueError(f"{name}: not on {dev}")
-            if not a.is_contiguous():
-                raise ValueError(f"{name}: not contiguous")
-        if points.shape[0] != normals.shape[0]:
-            raise ValueError("points and normals differ in length")
-        bad = [k for k in want if k not in self._GATHER_RADIANCE_OUTPUTS]
-        if bad:
-            raise ValueError(f"unknown outputs {bad}")
-        n, ns = int(points.shape[0]), int(nsamples)
-        if not 1 <= ns <= 65536:
-            raise ValueError("nsamples: 1..65536")
-
-        def shape(k):
-            return (n,) + tuple(ns if d == "s" else d for d in self._GATHER_RADIANCE_OUTPUTS[k][1])
-
-        given = dict(start or {})
-        bad = [k for k in given if k not in ("sum", "samples", "ray_casts")]
-        if bad:
-            raise ValueError(f"start: unknown entries {bad}")
-        for k, a in given.items():
-            dt = self._GATHER_RADIANCE_OUTPUTS[k][0]
-            if (not isinstance(a, torch.Tensor) or a.dtype != getattr(torch, dt) or a.device != dev
-                    or not a.is_contiguous() or tuple(a.shape) != shape(k)):
-                raise ValueError(f"start[{k!r}]: a contiguous {dt} tensor of {n} points on {dev} is required")
-        if int(first_sample) > 0 and ("sum" not in given or "samples" not in given):
-            raise ValueError("start: sum and samples are required when first_sample > 0")
-        out = {}
-        for k in tuple(want) + tuple(k for k in given if k not in want):
-            out[k] = given[k] if k in given else torch.empty(
-                shape(k), dtype=getattr(torch, self._GATHER_RADIANCE_OUTPUTS[k][0]), device=dev)
-        traced = torch.zeros(1, dtype=torch.int64, device=dev)
-        go = atr_gather_radiance_out(*[out[k].data_ptr() if k in out and n else None
-                                       for k in ("rgb", "sum", "samples", "ray_casts", "invalid", "sample_rgb",
-                                                 "dirs")], traced.data_ptr())
+        dev, n = self._xyz(points=points, normals=normals)
+        ns = int(nsamples)
+        out, traced, go = self._path_outputs(self._GATHER_RADIANCE_OUTPUTS, atr_gather_radiance_out, "points", dev, n,
+                                             ns, want, first_sample, dict(start or {}), ("sum", "samples"))
         if stream is None:
             stream = torch.cuda.current_stream(dev).cuda_stream
         check(lib().atr_gather_radiance(self.h, C.c_void_p(points.data_ptr()) if n else None,
@@ -1088,43 +1048,10 @@ class Engine:
         traced-ray count as a one-element int64 tensor); valid once the stream has run, e.g. after
         wait(). sh_irradiance(sh, normals) lights a normal from the result."""
         import torch
-        dev = torch.device("cuda", self.device)
-        if not isinstance(points, torch.Tensor) or points.dtype != torch.float32 or points.dim() != 2 \
-                or points.shape[1] != 3:
-            raise ValueError("points: an (n, 3) float32 tensor is required")
-        if points.device != dev:
-            raise ValueError(f"points: not on {dev}")
-        if not points.is_contiguous():
-            raise ValueError("points: not contiguous")
-        bad = [k for k in want if k not in self._PROBE_SH_OUTPUTS]
-        if bad:
-            raise ValueError(f"unknown outputs {bad}")
-        n, ns = int(points.shape[0]), int(nsamples)
-        if not 1 <= ns <= 65536:
-            raise ValueError("nsamples: 1..65536")
-
-        def shape(k):
-            return (n,) + tuple(ns if d == "s" else d for d in self._PROBE_SH_OUTPUTS[k][1])
-
-        given = dict(start or {})
-        bad = [k for k in given if k not in ("sum", "ray_casts")]
-        if bad:
-            raise ValueError(f"start: unknown entries {bad}")
-        for k, a in given.items():
-            dt = self._PROBE_SH_OUTPUTS[k][0]
-            if (not isinstance(a, torch.Tensor) or a.dtype != getattr(torch, dt) or a.device != dev
-                    or not a.is_contiguous() or tuple(a.shape) != shape(k)):
-                raise ValueError(f"start[{k!r}]: a contiguous {dt} tensor of {n} probes on {dev} is required")
-        if int(first_sample) > 0 and "sum" not in given:
-            raise ValueError("start: sum is required when first_sample > 0")
-        out = {}
-        for k in tuple(want) + tuple(k for k in given if k not in want):
-            out[k] = given[k] if k in given else torch.empty(
-                shape(k), dtype=getattr(torch, self._PROBE_SH_OUTPUTS[k][0]), device=dev)
-        traced = torch.zeros(1, dtype=torch.int64, device=dev)
-        go = atr_probe_sh_out(*[out[k].data_ptr() if k in out and n else None
-                                for k in ("sh", "sum", "ray_casts", "invalid", "sample_rgb", "dirs")],
-                              traced.data_ptr())
+        dev, n = self._xyz(points=points)
+        ns = int(nsamples)
+        out, traced, go = self._path_outputs(self._PROBE_SH_OUTPUTS, atr_probe_sh_out, "probes", dev, n, ns, want,
+                                             first_sample, dict(start or {}), ("sum",))
         if stream is None:
             stream = torch.cuda.current_stream(dev).cuda_stream
         check(lib().atr_probe_sh(self.h, C.c_void_p(points.data_ptr()) if n else None, n, ns, int(first_sample),
